@@ -8,12 +8,19 @@ Pippenger window parts from 4 (rank k computes windows [kW/N, (k+1)W/N) of all n
 the per-rank projective partial sums are all-gathered over RCCL and added on the host: one
 exchange step, so scaling is "strong" (total work fixed).
 
-Secondary line items (same JSON object): 10k batched width-256 Bandersnatch commits/s
-(config 3; the batch split across the N ranks, results all-gathered), and the CPU baseline:
-the reference's naive MSM restated in C (oracle/c/ref_curve.c) timed on a bounded sample on
-this host.
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the
+result line (metric, value, unit, ms_per_step, the MSM geometry, provenance). --dump-outputs DIR
+also writes what the last timed step returned as DIR/<name>.npy (the inputs are seeded, so two
+builds can be compared output for output).
 
-    python bench.py [--gpus N --steps K --warmup W]
+--full adds everything else to the same JSON object: the per-kernel pass with HIP events, the
+roofline figures, the result check, the variable-base and host-scalar lines, 10k batched
+width-256 Bandersnatch commits/s (config 3; the batch split across the N ranks, results
+all-gathered), the KZG / multiproof / IPA / verkle lines, and the CPU baselines: the reference's
+naive MSM restated in C (oracle/c/ref_curve.c) timed on a bounded sample on this host. The
+--no-* options below trim a --full run.
+
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 --gpus N > 1 starts N rank processes itself (torch.distributed.run on 127.0.0.1) unless a launcher
 already set WORLD_SIZE (then --gpus must equal it); --rehearse-one-gpu puts every rank on device 0.
@@ -69,6 +76,11 @@ def parse():
     # 20 untimed steps (~55 ms) before the timed region: measured 2.58-2.60 ms per step after 3,
     # 2.56 after 20, 2.53-2.55 after 100 on one box (the clock settles; profiles/r05/warmup/)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: per-kernel event pass, roofline, result check, "
+                         "variable-base / host-scalar / commit / KZG / multiproof / IPA / verkle lines, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's result as DIR/<name>.npy (float64)")
     ap.add_argument("--curve", default="bls12_381")
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--commit-batch", type=int, default=10000)
@@ -86,7 +98,7 @@ def parse():
     ap.add_argument("--no-verkle", action="store_true", help="skip the verkle-tree commitment line (8(f) rank 1)")
     ap.add_argument("--no-ipa", action="store_true", help="skip the single IPA prove/verify line (benches/ipa.rs)")
     ap.add_argument("--verkle-keys", type=int, default=1 << 16)
-    ap.add_argument("--verkle-reps", type=int, default=5, help="fresh trees / 1 % update rounds timed (medians)")
+    ap.add_argument("--verkle-reps", type=int, default=5, help="fresh trees / 1 %% update rounds timed (medians)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads of the Pippenger CPU baseline (0: min(16, cpu_count), one GPU's CPU share)")
     ap.add_argument("--cpu-sample", type=int, default=1 << 16, help="terms of the CPU naive MSM sample (~15 s)")
@@ -103,7 +115,20 @@ def parse():
                     help="N > 1 exchange: vc_comm (C ABI, RCCL) or torch.distributed all-gather")
     ap.add_argument("--msm-split", choices=["auto", "windows", "points"], default="auto",
                     help="N > 1: how one MSM splits over the ranks (auto: by N, from the one-card split probe)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the (affine xy limbs, infinity flag) a caller of the timed step receives, as
+    float64 arrays: msm_xy_u16.npy holds the 64-bit limbs cut into 16-bit words (little-endian word
+    order, each exact in float64), msm_inf.npy the flag."""
+    os.makedirs(path, exist_ok=True)
+    xy = np.ascontiguousarray(np.asarray(res[0], dtype="<u8"))
+    np.save(os.path.join(path, "msm_xy_u16.npy"), xy.view("<u2").astype(np.float64))
+    np.save(os.path.join(path, "msm_inf.npy"), np.array([int(res[1])], dtype=np.float64))
 
 
 # N > 1 split of the headline MSM, chosen per N from the one-card per-rank probe
@@ -1200,6 +1225,61 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     plan = eng.msm_last_plan()  # the geometry the timed MSMs ran (before the 1-term result check)
+    if world > 1:
+        tt = torch.tensor([dt], dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+        tm = torch.tensor(step_ms, dtype=torch.float64, device=dev)
+        dist.all_reduce(tm, op=dist.ReduceOp.MAX)  # per-step max over ranks
+        step_ms = tm.cpu().tolist()
+    ms_per_step = dt / a.steps * 1e3
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res)
+    c_bits, w_total, terms = plan["window_bits"], plan["windows"], plan["terms_per_point"]
+    prov = provenance()
+    out = {
+        "metric": METRIC,
+        "value": a.steps / dt,
+        "unit": "2^20-pt MSM/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": ms_per_step,
+        "ms_per_step_median": float(np.median(step_ms)),
+        "ms_per_step_min": float(np.min(step_ms)),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic (random subgroup bases s_i*G generated on device, uniform scalars < r)",
+        "config": {"workload": f"single 2^{a.log_n}-point {curve} G1 Pippenger MSM (configs[1])",
+                   "n_points": n, "curve": curve,
+                   "parallelism": (f"Pippenger-window slices x{world}" if split == "windows" else
+                                   f"point ranges x{world}") if world > 1 else "one GPU",
+                   "msm_split": split if world > 1 else None,
+                   "exchange": comm_kind,
+                   "window_bits": c_bits, "windows": w_total, "radix": plan["radix_mul"] << c_bits,
+                   "radix_form": f"{plan['radix_mul']} * 2^{c_bits}", "terms_per_point": terms,
+                   "precomputed_bases": (f"{w_total} x 2n window copies B^w P_i, B^w phi(P_i) with B = "
+                                         f"{plan['radix_mul']} * 2^{c_bits}, each signed copy (+-) one aligned "
+                                         f"128-B record of signed radix-2^30 limbs (x, y) "
+                                         f"({w_total * 2 * n * 2 * 128 / 1e9:.2f} GB), built once per base table "
+                                         "(a fixed CRS), untimed")
+                   if plan["shared_windows"] else None},
+        "provenance": prov,
+        "result_inf": int(res[1]),
+        "full": bool(a.full),
+    }
+    if not a.full:  # a plain run ends here: everything below is --full's
+        if comm is not None:
+            comm.close()
+        eng.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # kernel-timing pass: the same K steps with HIP events around every launch (on the stream the
     # kernels run on); its wall time is reported beside the headline as ms_per_step_with_events
     if world > 1:
@@ -1216,14 +1296,6 @@ def main():
     if not (int(res_e[1]) == int(res[1]) and np.array_equal(np.asarray(res_e[0]), np.asarray(res[0]))):
         raise SystemExit("bench: the kernel-timing pass gave a different MSM result")
     acc_mhz, acc_clk_n = eng.accumulate_clock()
-    if world > 1:
-        tt = torch.tensor([dt], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
-        tm = torch.tensor(step_ms, dtype=torch.float64, device=dev)
-        dist.all_reduce(tm, op=dist.ReduceOp.MAX)  # per-step max over ranks
-        step_ms = tm.cpu().tolist()
-    ms_per_step = dt / a.steps * 1e3
 
     # dominant kernel (bucket accumulation) device time, HIP events on the launch stream
     acc_ms, acc_n = eng.kernel_time("msm_accumulate")
@@ -1302,7 +1374,6 @@ def main():
     # wave-level, from the committed profile of this same command) x 64 lanes / its live time,
     # against the live issue peak of 4-cycle VALU work (v_mad_u64_u32; VCC adds issue the same,
     # plain 32-bit adds in half: tools/issueprobe.hip), i.e. lanes x SIMDs x clock / 4
-    c_bits, w_total, terms = plan["window_bits"], plan["windows"], plan["terms_per_point"]
     w_rank = (rank + 1) * w_total // world - rank * w_total // world
     madds = terms * n * w_rank if (world == 1 or split == "windows") else terms * (_phi - plo) * w_total
     mad_peak = eng.device_mad_rate()
@@ -1338,37 +1409,10 @@ def main():
             traffic = ke.get("by_class", {}).get("1", ke).get("hbm_bytes_per_launch")
             traffic_src = os.path.relpath(PMC_SUMMARY, ROOT)
 
-    prov = provenance()
-    out = {
-        "metric": METRIC,
-        "value": a.steps / dt,
-        "unit": "2^20-pt MSM/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": ms_per_step,
-        "ms_per_step_median": float(np.median(step_ms)),
-        "ms_per_step_min": float(np.min(step_ms)),
+    if out["config"]["precomputed_bases"]:
+        out["config"]["precomputed_bases"] += "; `variable_base` is the same MSM without them"
+    out.update({
         "ms_per_step_with_events": dt_events / a.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (random subgroup bases s_i*G generated on device, uniform scalars < r)",
-        "config": {"workload": f"single 2^{a.log_n}-point {curve} G1 Pippenger MSM (configs[1])",
-                   "n_points": n, "curve": curve,
-                   "parallelism": (f"Pippenger-window slices x{world}" if split == "windows" else
-                                   f"point ranges x{world}") if world > 1 else "one GPU",
-                   "msm_split": split if world > 1 else None,
-                   "exchange": comm_kind,
-                   "window_bits": c_bits, "windows": w_total, "radix": plan["radix_mul"] << c_bits,
-                   "radix_form": f"{plan['radix_mul']} * 2^{c_bits}", "terms_per_point": terms,
-                   "precomputed_bases": (f"{w_total} x 2n window copies B^w P_i, B^w phi(P_i) with B = "
-                                         f"{plan['radix_mul']} * 2^{c_bits}, each signed copy (+-) one aligned "
-                                         f"128-B record of signed radix-2^30 limbs (x, y) "
-                                         f"({w_total * 2 * n * 2 * 128 / 1e9:.2f} GB), built once per base table "
-                                         "(a fixed CRS), untimed; `variable_base` is the same MSM without them")
-                   if plan["shared_windows"] else None},
         "roofline": {"bound": "valu", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
                      "traffic_source": traffic_src,
@@ -1385,14 +1429,12 @@ def main():
         "accumulate_clock_mhz": acc_mhz or None,
         "accumulate_clock_source": (f"s_memtime / s_memrealtime stamps around one lane's loop, {acc_clk_n} "
                                     "timed launches (vc_ctx_accumulate_clock)") if acc_clk_n else None,
-        "provenance": prov,
         "pmc_libvkzg_sha256": (pmc or {}).get("libvkzg_sha256"),
         "pmc_same_library": bool(pmc) and (pmc or {}).get("libvkzg_sha256") == prov.get("libvkzg_sha256"),
-        "result_inf": int(res[1]),
         "result_check": check,
         "variable_base": variable,
         "host_scalars": host_line,
-    }
+    })
 
     progress("variable-base / host-scalar lines done")
     if not a.no_secondary:

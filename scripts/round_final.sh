@@ -24,9 +24,9 @@ if [ "${3:-}" != "noprof" ]; then
     mkdir -p $O/profiles_$RND && cp $R/profiles/$RND/pmc_summary.json $O/profiles_$RND/
 fi
 cd $R
-timeout -k 10 900 python -u bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 900 python -u bench.py --full > $O/bench.json 2> $O/bench.err
 echo bench-done
-timeout -k 10 900 python -u bench.py --gpus 2 --rehearse-one-gpu --steps 10 --warmup 3 --no-cpu-baseline > $O/rehearse_2rank.json 2> $O/rehearse_2rank.err
+timeout -k 10 900 python -u bench.py --gpus 2 --rehearse-one-gpu --steps 10 --warmup 3 --full --no-cpu-baseline > $O/rehearse_2rank.json 2> $O/rehearse_2rank.err
 echo rehearse-done
 timeout -k 10 300 python -u verkle-kzg_amd/tools/split_probe.py 1,2,8 > $O/split_probe.txt 2>&1
 echo split-done

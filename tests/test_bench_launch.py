@@ -38,6 +38,26 @@ def test_gpus_1_stays_one_process():
     assert j["n_gpus"] == 1 and [r["rank"] for r in j["ranks"]] == [0]
 
 
+def test_full_and_dump_outputs_are_options_and_steps_0_is_refused(tmp_path):
+    p = _run(["--launch-check", "--full", "--dump-outputs", str(tmp_path / "d"), "--steps", "2", "--warmup", "0"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert _line(p.stdout)["n_gpus"] == 1
+    p = _run(["--launch-check", "--steps", "0"])
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_dump_outputs_words_are_exact(tmp_path):
+    """the dumped float64 words give back every bit of the 64-bit limbs"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    xy = np.array([0, 1, 0xFFFFFFFFFFFFFFFF, 0x0123456789ABCDEF, 1 << 63, 0xFFFF0000FFFF0001] * 2, dtype=np.uint64)
+    bench.dump_outputs(str(tmp_path / "d"), (xy, 1))
+    words, inf = np.load(tmp_path / "d" / "msm_xy_u16.npy"), np.load(tmp_path / "d" / "msm_inf.npy")
+    assert words.dtype == np.float64 and words.shape == (48,) and inf.dtype == np.float64 and inf.tolist() == [1.0]
+    assert np.array_equal(words.astype("<u2").view("<u8"), xy)
+
+
 def test_gpus_disagreeing_with_world_size_is_refused():
     p = _run(["--gpus", "3", "--launch-check"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"}, drop=())
     assert p.returncode != 0
