@@ -1,6 +1,8 @@
 /* vc_scheme.h -- scheme-level C ABI of libvkzg.so: the reference's VectorCommitment
  * operations (/root/reference/vector-commit/src/lib.rs:70-174) for BN254 G1, with every
- * MSM / quotient / fold on the GPU and the serial Fiat-Shamir work on the host.
+ * MSM / quotient / fold on the GPU and the serial Fiat-Shamir work on the host.  KZG openings
+ * are verified with the BN254 pairing: one at a time on the host (vc_kzg_verify), or a batch on
+ * the GPU with one verdict per proof (vc_kzg_verify_many).
  *
  * Field elements (Fr) are 4 canonical little-endian u64 limbs; points are canonical affine
  * x[4], y[4] + a u8 identity flag (as in vc_msm.h).  All calls are synchronous and return
@@ -183,11 +185,49 @@ int vc_multiproof_prove_many(vc_ctx* ctx, int scheme, int table, size_t N, size_
 int vc_multiproof_verify_ipa(vc_ctx* ctx, int table, size_t N, size_t Q, const uint64_t* com_xy,
                              const uint8_t* com_inf, const uint64_t* z, const uint64_t* y,
                              const uint64_t* d_xy, uint8_t d_inf, const vc_ipa_proof* proof, int* result);
-/* KZG-scheme: the (commitment E - D, t) pair verify_point would check with pairings
- * (out of scope); returned so a caller can run its own pairing check. */
+/* KZG-scheme: the (commitment E - D, t) pair verify_point checks with pairings, for a caller
+ * that runs its own pairing check (vc_multiproof_verify_kzg below runs this library's). */
 int vc_multiproof_kzg_claim(vc_ctx* ctx, size_t N, size_t Q, const uint64_t* com_xy, const uint8_t* com_inf,
                             const uint64_t* z, const uint64_t* y, const uint64_t* d_xy, uint8_t d_inf,
                             uint64_t* c_xy, uint8_t* c_inf, uint64_t* t);
+
+/* ---------------------------------------------------------------- KZG verification (pairings)
+ * KZG::verify_point (kzg/mod.rs:165-189) with the BN254 optimal-ate pairing (csrc/pairing.hpp).
+ * G2 points: 16 canonical little-endian u64, x.c0[4] x.c1[4] y.c0[4] y.c1[4] (an Fq2 element is
+ * c0 + c1 u, u^2 = -1), on the twist y^2 = x^3 + 3 / (9 + u), plus a u8 identity flag.
+ * The check is e(proof, [s]_2) e(y G - C - p proof, H) == 1 with p = omega^point for
+ * point < size and the point itself otherwise (the reference's `<` at :172).
+ * A malformed key is VC_E_INVALID. A malformed proof entry -- a G1 point off the curve, a
+ * coordinate >= p, an Fr value >= r -- gives the verdict 0 and VC_OK. The identity is a valid G1
+ * input. Every call except vc_kzg_verify_many and vc_multiproof_verify_kzg is host code that
+ * needs no context and no GPU. */
+typedef struct vc_kzg_vk vc_kzg_vk;
+/* [secret]_2 = secret * H, what KZG::setup computes at kzg/mod.rs:122 (H: the G2 generator) */
+int vc_kzg_g2_from_secret(const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf);
+/* the verifying key of a domain of `size` (a power of two): checks [s]_2 (on the twist, of order
+ * r, not the identity), tabulates the Miller-loop lines of [s]_2 and H */
+int vc_kzg_vk_new(const uint64_t* g2_xy, uint8_t g2_inf, size_t size, vc_kzg_vk** vk);
+void vc_kzg_vk_free(vc_kzg_vk* vk);
+/* one opening on the host; result 1 = valid, 0 = invalid */
+int vc_kzg_verify(const vc_kzg_vk* vk, const uint64_t* com_xy, uint8_t com_inf, const uint64_t* point_fr,
+                  const uint64_t* proof_xy, uint8_t proof_inf, const uint64_t* y_fr, int* result);
+/* result 1 when prod e(P_i, Q_i) == 1 (lines computed on the fly). Q_i arbitrary points of G2:
+ * VC_E_INVALID for a G1 / G2 input off its curve or a G2 input outside the subgroup; identities
+ * on either side pair to one. */
+int vc_bn254_pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                           const uint8_t* g2_inf, int* result);
+/* n independent openings on the device, one lane each: results[i] = 1 / 0 as vc_kzg_verify of
+ * entry i (com_xy n x 8, points n x 4, proof_xy n x 8, y n x 4 u64; flags n). The key's line
+ * tables are uploaded into ctx on first use. */
+int vc_kzg_verify_many(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint64_t* com_xy, const uint8_t* com_inf,
+                       const uint64_t* points, const uint64_t* proof_xy, const uint8_t* proof_inf,
+                       const uint64_t* y, uint8_t* results);
+/* verify_multiproof for KZG (multiproof.rs:178-215): vc_multiproof_kzg_claim's computation,
+ * then vc_kzg_verify of (E - D, t, inner proof) */
+int vc_multiproof_verify_kzg(vc_ctx* ctx, const vc_kzg_vk* vk, size_t N, size_t Q, const uint64_t* com_xy,
+                             const uint8_t* com_inf, const uint64_t* z, const uint64_t* y, const uint64_t* d_xy,
+                             uint8_t d_inf, const uint64_t* kzg_proof_xy, uint8_t kzg_proof_inf,
+                             const uint64_t* kzg_y, int* result);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,18 @@
+// The KZG verifying key shared by the host verifier (pairing_host.cpp) and the batched device
+// verifier (pairing.hip).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "host/fr.hpp"
+#include "pairing.hpp"
+
+struct vc_kzg_vk {
+    uint64_t uid = 0;  // unique per key ever made (a freed key's address can come back): the
+                       // contexts key their uploaded copies of the tables on it
+    size_t size = 0;   // the domain
+    vk::Fr omega;      // its generator (Montgomery)
+    vk::bn::G2Aff s2;  // [s]_2
+    // Miller-loop lines of [s]_2, then of H
+    vk::bn::LineCoef lines[2 * vk::bn::PC::ATE_LINES];
+};

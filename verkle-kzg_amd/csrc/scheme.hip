@@ -2332,4 +2332,16 @@ int vc_multiproof_kzg_claim(vc_ctx* ctx, size_t N, size_t Q, const uint64_t* com
     return VC_OK;
 }
 
+int vc_multiproof_verify_kzg(vc_ctx* ctx, const vc_kzg_vk* vk, size_t N, size_t Q, const uint64_t* com_xy,
+                             const uint8_t* com_inf, const uint64_t* z, const uint64_t* y, const uint64_t* d_xy,
+                             uint8_t d_inf, const uint64_t* kzg_proof_xy, uint8_t kzg_proof_inf,
+                             const uint64_t* kzg_y, int* result) {
+    if (!vk || !result || !kzg_y || (!kzg_proof_xy && !kzg_proof_inf)) return VC_E_INVALID;
+    uint64_t c_xy[8], t[4];
+    uint8_t c_inf = 0;
+    VK_TRY(vc_multiproof_kzg_claim(ctx, N, Q, com_xy, com_inf, z, y, d_xy, d_inf, c_xy, &c_inf, t));
+    // KZG::verify_point takes no transcript (kzg/mod.rs:165-189): the claim and the proof decide
+    return vc_kzg_verify(vk, c_xy, c_inf, t, kzg_proof_xy, kzg_proof_inf, kzg_y, result);
+}
+
 }  // extern "C"

@@ -105,6 +105,14 @@ SIGNATURES = {
     "vc_multiproof_verify_ipa": (c_int, [c_void_p, c_int, c_size_t, c_size_t, P, P, P, P, P, ctypes.c_uint8, P,
                                          ctypes.POINTER(c_int)]),
     "vc_multiproof_kzg_claim": (c_int, [c_void_p, c_size_t, c_size_t, P, P, P, P, P, ctypes.c_uint8, P, P, P]),
+    "vc_kzg_g2_from_secret": (c_int, [P, P, P]),
+    "vc_kzg_vk_new": (c_int, [P, ctypes.c_uint8, c_size_t, ctypes.POINTER(c_void_p)]),
+    "vc_kzg_vk_free": (None, [c_void_p]),
+    "vc_kzg_verify": (c_int, [c_void_p, P, ctypes.c_uint8, P, P, ctypes.c_uint8, P, ctypes.POINTER(c_int)]),
+    "vc_bn254_pairing_check": (c_int, [c_size_t, P, P, P, P, ctypes.POINTER(c_int)]),
+    "vc_kzg_verify_many": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P]),
+    "vc_multiproof_verify_kzg": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, P, P, P, P, P, ctypes.c_uint8, P,
+                                         ctypes.c_uint8, P, ctypes.POINTER(c_int)]),
     # vc_comm.h
     "vc_comm_unique_id": (c_int, [P]),
     "vc_comm_init_rccl": (c_int, [c_int, c_int, c_int, P, ctypes.POINTER(c_void_p)]),

@@ -2,7 +2,8 @@
 
 Mirrors /root/reference/vector-commit/src: `IPA` (ipa/mod.rs), `KZG` (kzg/mod.rs),
 `LagrangeBasis` (lagrange_basis.rs), `TranscriptHasher` (transcript.rs),
-`prove_multiproof` / `verify_multiproof` (multiproof.rs), `to_data_item` (lib.rs:56-67).
+`prove_multiproof` / `verify_multiproof` / `verify_multiproof_kzg` (multiproof.rs), `to_data_item`
+(lib.rs:56-67). KZG openings are verified with pairings through `KZGVerifyingKey`.
 Same names, argument meaning and error behaviour (errors raise `VCError` where the Rust
 returns Err or panics). Curve: BN254 G1 (the reference's only instantiation).
 Points are canonical affine (x, y) tuples, the identity is None; field elements are ints.
@@ -301,8 +302,91 @@ class IPA:
 
 
 # ---------------------------------------------------------------- kzg/mod.rs
+def _fr_raw(x):
+    """4 limbs of x as given (verifier inputs: a value >= r must reach the library unreduced)"""
+    return ints_to_limbs([int(x) & _M256], 4)[0].copy()
+
+
+def _g2_array(Q):
+    """((x0, x1), (y0, y1)) | None -> (16 u64 limbs, identity flag) in the ABI's G2 layout"""
+    xy = np.zeros(16, dtype=np.uint64)
+    if Q is None:
+        return xy, 1
+    (x0, x1), (y0, y1) = Q
+    xy[:] = ints_to_limbs([int(v) & _M256 for v in (x0, x1, y0, y1)], 4).reshape(16)
+    return xy, 0
+
+
+def kzg_g2_from_secret(secret):
+    """[secret]_2 = secret * H (kzg/mod.rs:122) as ((x.c0, x.c1), (y.c0, y.c1)), None = identity."""
+    xy = np.zeros(16, dtype=np.uint64)
+    inf = np.zeros(1, dtype=np.uint8)
+    check(lib().vc_kzg_g2_from_secret(_p(_fr(secret)), _p(xy), _p(inf)), "kzg_g2_from_secret")
+    if inf[0]:
+        return None
+    v = [limbs_to_int(xy[4 * k:4 * k + 4]) for k in range(4)]
+    return ((v[0], v[1]), (v[2], v[3]))
+
+
+def pairing_check(pairs):
+    """prod e(P_i, Q_i) == 1 for pairs of (G1 point | None, G2 point | None); VCError for an
+    input off its curve or a G2 point outside the subgroup. Host code."""
+    n = len(pairs)
+    g1, g1inf = _pt_arrays([a for a, _ in pairs]) if n else (np.zeros((1, 8), dtype=np.uint64), np.zeros(1, dtype=np.uint8))
+    g2 = np.zeros((max(n, 1), 16), dtype=np.uint64)
+    g2inf = np.zeros(max(n, 1), dtype=np.uint8)
+    for i, (_, Q) in enumerate(pairs):
+        g2[i], g2inf[i] = _g2_array(Q)
+    res = ctypes.c_int()
+    check(lib().vc_bn254_pairing_check(n, _p(g1), _p(g1inf), _p(g2), _p(g2inf), ctypes.byref(res)), "pairing_check")
+    return bool(res.value)
+
+
+class KZGVerifyingKey:
+    """[s]_2 and the domain size: all KZG::verify_point needs (no SRS, no secret). Host code
+    except verify_many, which takes an Engine. VCError(VC_E_INVALID) for a malformed [s]_2."""
+
+    def __init__(self, g2, size):
+        xy, inf = _g2_array(g2)
+        h = ctypes.c_void_p()
+        self.h = None
+        check(lib().vc_kzg_vk_new(_p(xy), inf, size, ctypes.byref(h)), "kzg_vk_new")
+        self.h, self.size, self.g2 = h, size, g2
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().vc_kzg_vk_free(self.h)
+            self.h = None
+
+    def verify_point(self, commitment, point, proof, transcript=None):
+        """:165-189; proof = {"proof": point, "y": int}. The transcript is unused, as in the reference."""
+        cxy, cinf = _pt_arrays([commitment])
+        pxy, pinf = _pt_arrays([proof["proof"]])
+        res = ctypes.c_int()
+        check(lib().vc_kzg_verify(self.h, _p(cxy), int(cinf[0]), _p(_fr_raw(point)), _p(pxy), int(pinf[0]),
+                                  _p(_fr_raw(proof["y"])), ctypes.byref(res)), "kzg_verify")
+        return bool(res.value)
+
+    def verify(self, commitment, index, proof):
+        return self.verify_point(commitment, index, proof)
+
+    def verify_many(self, engine, commitments, points, proofs):
+        """n openings on the GPU, one verdict each (vc_kzg_verify_many) -> list of bool."""
+        n = len(proofs)
+        if n == 0:
+            return []
+        cxy, cinf = _pt_arrays(commitments)
+        pxy, pinf = _pt_arrays([pr["proof"] for pr in proofs])
+        pts = ints_to_limbs([int(p) & _M256 for p in points], 4)
+        ys = ints_to_limbs([int(pr["y"]) & _M256 for pr in proofs], 4)
+        out = np.zeros(n, dtype=np.uint8)
+        check(lib().vc_kzg_verify_many(engine.h, self.h, n, _p(cxy), _p(cinf), _p(pts), _p(pxy), _p(pinf), _p(ys),
+                                       _p(out)), "kzg_verify_many")
+        return [bool(v) for v in out]
+
+
 class KZG:
-    """KZG<Bn254, ...> prover side (pairing verification is out of scope: see DESIGN.md)."""
+    """KZG<Bn254, ...>: commit, open and (through KZGVerifyingKey) verify with pairings."""
 
     def __init__(self, engine, max_items, secret=100):
         self.engine = engine
@@ -350,6 +434,26 @@ class KZG:
         check(lib().vc_kzg_prove_all_points(self.engine.h, self.table, self.size, _p(ev), len(data.evals), mode,
                                             _p(xy), _p(inf), _p(ys), ctypes.byref(cnt)), "kzg_prove_all_points")
         return [{"proof": _pt(xy[i], inf[i]), "y": limbs_to_int(ys[i])} for i in range(cnt.value)]
+
+    def g2(self):
+        """[s]_2 of the setup (kzg/mod.rs:122)."""
+        return kzg_g2_from_secret(self.secret)
+
+    def verifying_key(self):
+        if getattr(self, "_vk", None) is None:
+            self._vk = KZGVerifyingKey(self.g2(), self.size)
+        return self._vk
+
+    def verify_point(self, commitment, point, proof, transcript=None):
+        """KZG::verify_point (:165-189) on the host."""
+        return self.verifying_key().verify_point(commitment, point, proof)
+
+    def verify(self, commitment, index, proof):
+        return self.verify_point(commitment, index, proof)
+
+    def verify_many(self, commitments, points, proofs):
+        """One verdict per opening, the batch on the GPU (test_amortized_proof's loop)."""
+        return self.verifying_key().verify_many(self.engine, commitments, points, proofs)
 
     def quotient(self, point, data):
         ev = data.limbs()
@@ -409,6 +513,22 @@ def verify_multiproof(vc, vqueries, mp):
     check(lib().vc_multiproof_kzg_claim(vc.engine.h, N, Q, _p(cxy), _p(cinf), _p(z), _p(y), _p(dxy), int(dinf[0]),
                                         _p(oxy), _p(oinf), _p(t)), "multiproof_kzg_claim")
     return {"commitment": _pt(oxy, oinf[0]), "t": limbs_to_int(t)}
+
+
+def verify_multiproof_kzg(vc, vqueries, mp):
+    """verify_multiproof (multiproof.rs:178-215) for KZG, pairing check included -> bool.
+    vc: a KZG (its verifying key is used); vqueries: (commitment, z, y); mp: {"proof", "d"}."""
+    N, Q = vc.size, len(vqueries)
+    cxy, cinf = _pt_arrays([q[0] for q in vqueries])
+    z = np.array([int(q[1]) for q in vqueries], dtype=np.uint64)
+    y = ints_to_limbs([int(q[2]) % R_BN254 for q in vqueries], 4)
+    dxy, dinf = _pt_arrays([mp["d"]])
+    pxy, pinf = _pt_arrays([mp["proof"]["proof"]])
+    res = ctypes.c_int()
+    check(lib().vc_multiproof_verify_kzg(vc.engine.h, vc.verifying_key().h, N, Q, _p(cxy), _p(cinf), _p(z), _p(y),
+                                         _p(dxy), int(dinf[0]), _p(pxy), int(pinf[0]), _p(_fr_raw(mp["proof"]["y"])),
+                                         ctypes.byref(res)), "multiproof_verify_kzg")
+    return bool(res.value)
 
 
 class MultiproofSet:
