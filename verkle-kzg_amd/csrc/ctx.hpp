@@ -206,6 +206,7 @@ enum WsSlot {
     WS_SP_ITEMS,  // to_data_item of the sparse commits' rows (msm_batch_sparse_items)
     WS_NORM_CNT,  // the verkle normalisation's arrival counter (zero between launches)
     WS_NORM_TOT,  // its block products and per-block cofactors (device scan)
+    WS_STARTS,    // the accumulate threads' start records (msm.hip AccStart), written by k_sort_fine
     WS_COUNT_
 };
 

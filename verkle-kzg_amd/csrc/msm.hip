@@ -4,7 +4,8 @@
 // Pipeline (all on the ctx stream, one host sync at the end):
 //   k_sort_*         scalar -> W signed c-bit digits (|d| <= 2^(c-1)); two-pass LDS counting
 //                    sort of the (window, bucket) keys: sorted[] = i | sign<<31 grouped by
-//                    bucket, offsets[] = bucket starts (all windows concatenated)
+//                    bucket, offsets[] = bucket starts (all windows concatenated), and the
+//                    start record of every accumulate thread (AccStart)
 //   k_msm_accumulate every thread sums exactly M consecutive sorted entries (mixed adds
 //                    of affine bases gathered from HBM), writing complete buckets directly
 //                    and bucket pieces that straddle a thread boundary to side slots
@@ -341,9 +342,20 @@ __global__ void __launch_bounds__(1024) k_sort_coarse_st(Src src, uint32_t n, in
     }
 }
 
+// Start record of accumulate thread t (first sorted entry t M), written by the fine sort pass
+// from the bucket starts it holds in LDS: the bucket b that holds entry t M, that bucket's
+// [begin, end) in the sorted entries, and the end of bucket b + 1 (0: b is the last bucket of
+// its coarse bin, whose block does not know it). The accumulate reads its record instead of
+// searching offsets[]. One aligned 16-B load.
+struct alignas(16) AccStart {
+    uint32_t b, begin, end, next_end;
+};
+
 // one block per coarse bin; offsets[g * 2^FB + f] = start of fine bucket f of bin g. Block 0
 // also clears the accumulate's chain_max word (no separate memset in the pipeline). Blocks of
 // 256 or 1024 threads (large bins): the 256 fine counters are scanned by the first 256.
+// starts != nullptr: the block also writes the start records of the accumulate threads (M sorted
+// entries each) whose first entry lies in its bin.
 // cap > 0: a bin of at most cap entries is scattered into LDS (dynamic, cap words) and written
 // out in one coalesced pass -- the direct scatter wrote each bucket's 4-B entries one at a time
 // over the block's life, and the partly written lines left L2 several times (PMC WRITE_SIZE
@@ -352,7 +364,8 @@ template <class T>
 __global__ void __launch_bounds__(1024) k_sort_fine(const T* __restrict__ tmp, const uint32_t* __restrict__ base,
                                                    uint32_t nblk, uint32_t bins, uint32_t FB,
                                                    uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted,
-                                                   uint32_t* __restrict__ zero_word, uint32_t cap, uint32_t regs_ok) {
+                                                   uint32_t* __restrict__ zero_word, uint32_t cap, uint32_t regs_ok,
+                                                   AccStart* __restrict__ starts, uint32_t M) {
     __shared__ uint32_t h[256], x[256];
     extern __shared__ uint32_t stage[];
     const uint32_t g = blockIdx.x, F = 1u << FB, t = threadIdx.x;
@@ -404,6 +417,29 @@ __global__ void __launch_bounds__(1024) k_sort_fine(const T* __restrict__ tmp, c
     const uint32_t excl = cnt_lane ? x[t] - v : 0u;
     if (t < F) offsets[(size_t)g * F + t] = start + excl;
     if (g == bins - 1 && t == 0) offsets[(size_t)bins * F] = end;
+    // start records (AccStart) of the accumulate threads u whose first entry u M lies in this bin:
+    // their bucket is the first fine bucket whose inclusive count passes u M - start (so never an
+    // empty one), searched in the LDS scan -- a thread per record, whether one bucket holds many
+    // thread starts (equal scalars) or runs of empty buckets lie between two of them
+    if (starts != nullptr) {
+        for (uint64_t u = ((uint64_t)start + M - 1) / M + t; u * M < end; u += blockDim.x) {
+            const uint32_t rel = (uint32_t)(u * M) - start;
+            uint32_t lo = 0, hi = F - 1;  // x[F - 1] = end - start > rel
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (x[mid] > rel) hi = mid;
+                else lo = mid + 1;
+            }
+            AccStart r;
+            r.b = g * F + lo;
+            r.begin = start + (lo ? x[lo - 1] : 0u);
+            r.end = start + x[lo];
+            r.next_end = lo + 1 < F ? start + x[lo + 1] : 0u;
+            starts[u] = r;
+        }
+        // the sentinel: thread T = ceil(L / M), the first one that does not run
+        if (g == bins - 1 && t == 0) starts[((uint64_t)end + M - 1) / M] = AccStart{bins * F, end, end, 0u};
+    }
     __syncthreads();
     if (cnt_lane) h[t] = excl;  // cursors
     __syncthreads();
@@ -509,7 +545,7 @@ __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
     typename Fast29<C>::type::Acc* __restrict__ buckets, typename Fast29<C>::type::Acc* __restrict__ carry_in,
     uint8_t* __restrict__ through, typename Fast29<C>::type::Acc* __restrict__ owner_piece,
     uint32_t* __restrict__ owner_bucket, uint32_t* __restrict__ chain_max, uint32_t merge,
-    unsigned long long* __restrict__ clk) {
+    unsigned long long* __restrict__ clk, const AccStart* __restrict__ starts) {
     using FC = typename Fast29<C>::type;
     using Aff = BT;
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -525,16 +561,30 @@ __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
     uint32_t e = min(k + M, L);
     owner_bucket[t] = NONE;
     through[t] = 0;
-    // bucket b with offsets[b] <= k < offsets[b+1]
-    uint32_t lo = 0, hi = NBtot;  // invariant offsets[lo] <= k < offsets[hi]
-    while (hi - lo > 1) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (offsets[mid] <= k) lo = mid;
-        else hi = mid;
+    // bucket b with offsets[b] <= k < offsets[b+1]: the thread's start record when the sort wrote
+    // them (uniform over the grid), else a search of offsets[] (~log2 NBtot dependent loads)
+    uint32_t b, bbeg, bend, nxt;  // nxt: the end of bucket b + 1, loaded a bucket ahead (0: not known)
+    if (starts != nullptr) {
+        const AccStart s = starts[t];
+        b = s.b;
+        bbeg = s.begin;
+        bend = s.end;
+        nxt = s.next_end;
+    } else {
+        uint32_t lo = 0, hi = NBtot;  // invariant offsets[lo] <= k < offsets[hi]
+        while (hi - lo > 1) {
+            uint32_t mid = (lo + hi) >> 1;
+            if (offsets[mid] <= k) lo = mid;
+            else hi = mid;
+        }
+        b = lo;
+        bbeg = offsets[b];
+        bend = offsets[b + 1];
+        nxt = 0;
     }
-    uint32_t b = lo;
-    uint32_t bend = offsets[b + 1];
-    bool left_open = offsets[b] < k;
+    // threads from the bucket's owner (the thread that holds its first entry) to this one: 0 when
+    // the bucket begins here, else its first piece is a carry piece (the bucket is open to the left)
+    uint32_t left_open = t - bbeg / M;
     typename FC::Acc acc = FC::zero();
     // entry j < nphi: bases[j]; j >= nphi: phi[j - nphi] (the GLV endomorphism images)
     auto base_of = [&](uint32_t j) -> const Aff* { return j < nphi ? bases + j : phi + (j - nphi); };
@@ -566,6 +616,7 @@ __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
         }
     };
     uint32_t idx = sorted[k];
+    uint32_t idx2 = sorted[min(k + 1, e - 1)];
     Pre P = fetch(idx);
     uint32_t my_through = 0, own_b = NONE;  // for the merge after the loop
     while (true) {
@@ -573,10 +624,13 @@ __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
         typename FC::Aff Q;
         if constexpr (SN || SP || FBE) Q = P;
         else Q = FC::load(&P);
-        if (k + 1 < e) {  // prefetch next base
-            idx = sorted[k + 1];
-            P = fetch(idx);
-        }
+        // prefetch the next base; its entry index was loaded an iteration earlier, so the gather's
+        // address waits on no load. Unconditional (the thread's last entry again at its end): under
+        // `if (k + 1 < e)` the loaded registers were copied into P's behind waits on the loads
+        // just issued
+        idx = idx2;
+        idx2 = sorted[min(k + 2, e - 1)];
+        P = fetch(idx);
         acc = FC::madd(acc, Q, !SN && !SP && (cur >> 31) != 0);
         k++;
         if (k == bend || k == e) {
@@ -587,22 +641,29 @@ __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
                 carry_in[t] = acc;
                 my_through = right_open ? 2 : 1;
                 through[t] = (uint8_t)my_through;  // 1: carry piece ending here, 2: bucket continues
-                if (!right_open) {  // chain end: chain length = carry threads of this bucket
-                    const uint32_t L = t - offsets[b] / M;
-                    if (L >= 2) atomicMax(chain_max, L);
-                }
+                // chain end: chain length = carry threads of this bucket
+                if (!right_open && left_open >= 2) atomicMax(chain_max, left_open);
             } else {
                 owner_piece[t] = acc;
                 owner_bucket[t] = b;
                 own_b = b;  // acc keeps the owner piece: it is the thread's last bucket
             }
             if (k == e) break;
-            left_open = false;
+            left_open = 0;
             acc = FC::zero();
-            do {
+            // the next bucket's end was loaded when this one was entered, so no load issued here is
+            // needed before the next add. Slow path: empty buckets follow (their ends are <= k) or
+            // the end is not known (0): walk offsets[] (k < e <= offsets[NBtot] ends it)
+            if (nxt > k) {
                 b++;
-                bend = offsets[b + 1];
-            } while (bend <= k);
+                bend = nxt;
+            } else {
+                do {
+                    b++;
+                    bend = offsets[b + 1];
+                } while (bend <= k);
+            }
+            nxt = offsets[min(b + 2, NBtot)];
         }
     }
     if (stamp) {
@@ -1168,8 +1229,8 @@ template <class Src>
 static int sort_entries(vc_ctx* ctx, Lane L, Src src, uint32_t nv, int c, int wb, int we, uint32_t FB,
                         uint32_t NBC, uint32_t nblk, uint32_t chunk, uint32_t stride, uint32_t wps, size_t ncnt,
                         uint32_t* counts, uint32_t* base, void* tmp, uint32_t* offsets, uint32_t* sorted,
-                        uint32_t* zero_word, bool coarse_stage = false, bool counts_ready = false,
-                        uint32_t sets_split = 1) {
+                        uint32_t* zero_word, AccStart* starts, uint32_t M, bool coarse_stage = false,
+                        bool counts_ready = false, uint32_t sets_split = 1) {
     hipStream_t st = L.st;
     if (stride && wps == 0) return VC_E_INVALID;
     const uint32_t bins = (stride ? ((uint32_t)we + wps - 1) / wps : (uint32_t)(we - wb)) * NBC;
@@ -1229,17 +1290,20 @@ static int sort_entries(vc_ctx* ctx, Lane L, Src src, uint32_t nv, int c, int wb
                          NBC, nblk, stride, wps, chunk, counts, base, static_cast<uint32_t*>(tmp), s * bins_l, bins_l);
         }
         VK_LAUNCH_ON(ctx, st, "msm_sort_fine", k_sort_fine<uint32_t>, bins, fblk, cap * 4,
-                     static_cast<const uint32_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs);
+                     static_cast<const uint32_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs,
+                     starts, M);
     } else if (narrow) {
         VK_LAUNCH_ON(ctx, st, "msm_sort_coarse", (k_sort_coarse<Src, uint32_t>), nblk, sblk, lds, src, nv, c, wb, we,
                      FB, NBC, nblk, stride, wps, chunk, base, static_cast<uint32_t*>(tmp));
         VK_LAUNCH_ON(ctx, st, "msm_sort_fine", k_sort_fine<uint32_t>, bins, fblk, cap * 4,
-                     static_cast<const uint32_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs);
+                     static_cast<const uint32_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs,
+                     starts, M);
     } else {
         VK_LAUNCH_ON(ctx, st, "msm_sort_coarse", (k_sort_coarse<Src, uint64_t>), nblk, sblk, lds, src, nv, c, wb, we,
                      FB, NBC, nblk, stride, wps, chunk, base, static_cast<uint64_t*>(tmp));
         VK_LAUNCH_ON(ctx, st, "msm_sort_fine", k_sort_fine<uint64_t>, bins, fblk, cap * 4,
-                     static_cast<const uint64_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs);
+                     static_cast<const uint64_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs,
+                     starts, M);
     }
     return VC_OK;
 }
@@ -1475,6 +1539,8 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
     VK_TRY(ws[WS_THROUGH].ensure((size_t)(Tmax + 8)));
     VK_TRY(ws[WS_OWNER].ensure((size_t)(Tmax + 8) * sizeof(RAcc)));
     VK_TRY(ws[WS_OWNER_B].ensure((size_t)(Tmax + 8) * 4));
+    VK_TRY(ws[WS_STARTS].ensure((size_t)(Tmax + 8) * sizeof(AccStart)));  // threads < T <= Tmax and the sentinel T
+    AccStart* const starts = ws[WS_STARTS].as<AccStart>();
     VK_TRY(ws[WS_SEG].ensure((size_t)S * Wr * sizeof(RAcc)));
     VK_TRY(ws[WS_TREE].ensure((size_t)S * Wr * sizeof(RAcc)));
     VK_TRY(ws[WS_WIN].ensure((size_t)Wr * msm_tail_plan(S, (uint32_t)Wr, J, nU, Fast29<C>::type::quad, Lseg == 1).slots *
@@ -1535,14 +1601,14 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
                         sl.wps, ncnt,
                         ws[WS_COUNTS].as<uint32_t>(),
                         ws[WS_CURSOR].as<uint32_t>(), ws[WS_DIGITS].p, sl.offsets,
-                        ws[WS_SORTED].as<uint32_t>(), sl.chain_max, cstage, counts_ready,
+                        ws[WS_SORTED].as<uint32_t>(), sl.chain_max, starts, M, cstage, counts_ready,
                         sl.shared ? (uint32_t)Wr : 1u));
     // entry count L = offsets[NBtot] stays on the device; grids are sized for L <= nv*W;
     // chain_max was cleared by k_sort_fine
     if (acc_wait) VK_CHECK_HIP(hipStreamWaitEvent(st, acc_wait, 0));
     VK_LAUNCH_ON(ctx, st, "msm_accumulate", (k_msm_accumulate<C, BT>), (Tmax + 255) / 256, 256, 0, bases, phi, nphi,
                  ws[WS_SORTED].as<uint32_t>(), sl.offsets, NBtot, M, sl.buckets, sl.carry, sl.through, sl.owner,
-                 sl.owner_b, sl.chain_max, acc_merge(), (unsigned long long*)ctx->clk_slot());
+                 sl.owner_b, sl.chain_max, acc_merge(), (unsigned long long*)ctx->clk_slot(), starts);
     if (acc_done) VK_CHECK_HIP(hipEventRecord(acc_done, st));
     // chains up to 2^guard carry pieces are walked serially by their owners; longer ones
     // (adversarial scalars) take the pointer-jumping path in slice_finish
@@ -2441,7 +2507,7 @@ static int sparse_commit_dev(vc_ctx* ctx, Table* t, size_t batch, const uint64_t
         VK_LAUNCH(ctx, "sparse_accumulate", (k_msm_accumulate<C, FA>), (Tmax + 255) / 256, 256, 0, tab, tab, 0xffffffffu,
                   d_ent.as<uint32_t>(), d_off.as<uint32_t>(), (uint32_t)nch, M, d_raw.as<RAcc>(), d_carry.as<RAcc>(),
                   d_thr.as<uint8_t>(), d_own.as<RAcc>(), d_ownb.as<uint32_t>(), chain_max, acc_merge(),
-                  (unsigned long long*)nullptr);
+                  (unsigned long long*)nullptr, (const AccStart*)nullptr);  // rows are not sorted here: the search
         // straddling chunks merged by the serial walk of their owners, no chain limit: a chunk holds at
         // most CHNZ x W entries, so it spans at most CHNZ W / M + 2 threads. (The pointer-jumping rounds
         // used before read the longest chain back first -- a host sync per level -- and ran ~3 guarded
