@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "vc_msm.h"
+#include "vc_scheme.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -63,6 +64,82 @@ int vc_verkle_debug_nodes(vc_verkle* t, size_t max, uint8_t* type, int32_t* leve
 int vc_verkle_debug_ext_stage(vc_verkle* t, int reps, double* us);
 /* node counts (diagnostics): internal, extension, dirty */
 int vc_verkle_stats(const vc_verkle* t, size_t* internal, size_t* extension, size_t* dirty);
+
+/* ---------------------------------------------------------------- tree proofs
+ * A proof shows that n keys, all present in the tree, map to their values under the root
+ * commitment: one multiproof (vc_scheme.h, multiproof.rs) over the openings on the keys' paths.
+ * The reference declares this (verkle-tree/src/lib.rs:140-152, an empty impl block) and stops.
+ * Proofs of absence are out of scope: a key vc_verkle_get does not find is VC_E_INVALID.
+ *
+ * Path of key K (N units): the nodes vc_verkle_get / vc_verkle_path walk. d = the number of
+ * internal nodes on it, the root I_0 included (1 <= d <= N - 1); I_{j+1} is the child of I_j at
+ * position K[j] (also below the reference's level-skipping splits: position j is always indexed
+ * with K[j]); the child of I_{d-1} at K[d-1] is the extension E whose stem is K, the whole key
+ * (lib.rs:61-67). u = K[N-1], half = (u < N / 2) ? 1 : 2, C_half = the extension's c1 or c2
+ * commitment (node.rs:216-244), (lo, hi) = the value's bytes 0..16 and 16..32 as LE integers.
+ *
+ * Queries (commitment, z, y) of K, in this order, all over the domain of size 256 (a row of width
+ * 4 or N is the same group element as its zero-padded width-256 row, so it is opened there):
+ *   1. for j = 0 .. d-1:  C(I_j),  z = K[j],            y = to_data_item(C(next)), next = I_{j+1}, or E
+ *                                                           for j = d-1
+ *   2.                    C(E),    z = 0,               y = 1
+ *   3.                    C(E),    z = 1,               y = from_le_bytes_mod_order(K) (node.rs:248)
+ *   4.                    C(E),    z = 1 + half,        y = to_data_item(C_half)
+ *   5.                    C_half,  z = (2 u) % N,       y = lo
+ *   6.                    C_half,  z = (2 u + 1) % N,   y = hi
+ * The query list is the keys' queries in the caller's key order, a (node, z) pair that was emitted
+ * before left out (a repeated key adds nothing); that order is the multiproof transcript's. Nodes
+ * are told apart by where they sit: an internal node at position j by the units K[0..j), an
+ * extension by its full key, a C_half by (full key, half). The `% N` folding of node.rs:231-232
+ * can make two leaves of one extension share a slot; a key whose row no longer holds (lo, hi) at
+ * its two slots cannot be proven (VC_E_INVALID).
+ *
+ * The proof: depth[i] = d of key i; the distinct commitments other than the root in
+ * first-occurrence order of that walk (per key: the internal nodes at positions 1 .. d-1, then
+ * C(E), then C_half); the multiproof's D; and the inner proof at the multiproof's t -- an IPA proof
+ * (scheme 0) or the KZG proof point and y (scheme 1). All arrays are the caller's. */
+typedef struct {
+    size_t n_keys;      /* in: the keys proven (the length of depth) */
+    uint8_t* depth;     /* n_keys */
+    size_t n_com;       /* prove: in = the capacity of com_xy / com_inf, out = the commitments written */
+    uint64_t* com_xy;   /* n_com x 8 u64, canonical affine */
+    uint8_t* com_inf;   /* n_com identity flags */
+    uint64_t d_xy[8];
+    uint8_t d_inf;
+    vc_ipa_proof ipa;   /* scheme 0: rounds = 8 with its four arrays */
+    uint64_t kzg_proof_xy[8];  /* scheme 1 */
+    uint8_t kzg_proof_inf;
+    uint64_t kzg_y[4];
+} vc_verkle_proof;
+/* host only, no GPU: the commitments (n_com) and queries a proof of these n keys (n x N bytes)
+ * holds; VC_E_INVALID for an absent or unprovable key */
+int vc_verkle_proof_size(const vc_verkle* t, const uint8_t* keys, size_t n, size_t* n_com, size_t* n_queries);
+/* scheme 0: IPA, `table` holds the 257 points g[0..256], q; scheme 1: KZG, `table` is the
+ * size-256 Lagrange SRS; any other scheme or table size is VC_E_TABLE. It must be the table the tree is
+ * committed with. If any node is dirty the tree is first committed as vc_verkle_commitment does
+ * with this context and table. root_xy / root_inf: the root the proof is against. Nothing is
+ * written when a key is absent or unprovable. The field phase reads the opened rows' non-zeros
+ * where they are (the children's items in the device mirror) instead of building Q x 256 rows. */
+int vc_verkle_prove(vc_ctx* ctx, int scheme, int table, vc_verkle* t, const uint8_t* keys, size_t n,
+                    uint64_t* root_xy, uint8_t* root_inf, vc_verkle_proof* out);
+/* needs no tree: rebuilds the query list from (root, keys, values32, proof->depth, the proof's
+ * commitments) as above -- y of queries 1 and 4 is to_data_item of the proof's commitments
+ * (vc_to_data_item_batch) -- and runs vc_multiproof_verify_ipa (scheme 0, `table` as for prove) or
+ * vc_multiproof_verify_kzg (scheme 1, vk of the size-256 domain; `table` unused). *result = 1
+ * valid, 0 invalid. Verdict 0 with VC_OK for: a depth outside 1..N-1; two keys that put different
+ * node kinds, or two different extensions, at one position; a (node, z) pair the keys give two
+ * different y; a commitment count that does not match the walk; a malformed point; an inner
+ * verification that fails. VC_E_INVALID only for null or inconsistent arguments (n_keys != n). */
+int vc_verkle_verify(vc_ctx* ctx, int scheme, int table, const vc_kzg_vk* vk, int key_len, const uint64_t* root_xy,
+                     uint8_t root_inf, const uint8_t* keys, const uint8_t* values32, size_t n,
+                     const vc_verkle_proof* proof, int* result);
+/* diagnostics (nothing in the product path calls it): the prover's query list -- commitments
+ * (max_q x 8, max_q), z (max_q), y (max_q x 4) -- and, if rows is not NULL, its zero-padded dense
+ * rows (max_q x 256 x 4 u64) on the host, built from the tree's host arrays (the device mirror is
+ * read back first); *Q = the number of queries (VC_E_RANGE if above max_q). Commits a dirty tree
+ * first, as vc_verkle_prove. */
+int vc_verkle_proof_queries(vc_ctx* ctx, int table, vc_verkle* t, const uint8_t* keys, size_t n, size_t max_q,
+                            uint64_t* com_xy, uint8_t* com_inf, uint64_t* z, uint64_t* y, uint64_t* rows, size_t* Q);
 
 #ifdef __cplusplus
 }

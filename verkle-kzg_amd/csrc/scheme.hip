@@ -1987,6 +1987,151 @@ static int mp_prove(vc_ctx* ctx, int scheme, Table* t, size_t N, size_t Q, const
     return st;
 }
 
+// ---- the sparse field phase (scheme_internal.hpp MpSparse; the verkle tree proofs): the same sums
+// S[row][k] = sum r^i f_i[k] as k_mp_chunk's, with f_i[k] looked up instead of streamed -- a verkle
+// opening's row has a handful of non-zeros of 256, most of them items already in the tree's device
+// mirror, and many queries open the same row at different points; so no Q x N matrix is built,
+// uploaded or read. Each distinct row has a descriptor of 2 N / 32 words: its non-zero columns as a
+// bitmap, and per bitmap word the index of that word's first non-zero in the source list. A query
+// names its row; lane k of a block tests bit k, ranks it with a popcount and loads the value from
+// the mirror's items or the literals. The plan (queries sorted by point, chunks of one point's
+// queries, the reduce pass over a point's chunks) is k_mp_chunk's own MpPlan, and so is the
+// arithmetic: mp_block over blocks of MP_SP_LZ queries, an absent element entering as zero. A block
+// in which no lane of the wave has an element is skipped (extension rows live in columns 0..3: three
+// of the four waves of a 256-column block).
+constexpr uint32_t MP_SP_LZ = 4;
+__global__ void __launch_bounds__(256) k_mp_sparse_chunk(const uint32_t* __restrict__ desc, const uint32_t* __restrict__ q_row,
+                                                        const uint32_t* __restrict__ srcs,
+                                                        const uint64_t* __restrict__ item,
+                                                        const uint64_t* __restrict__ aux,
+                                                        const uint32_t* __restrict__ rp, const uint32_t* __restrict__ order,
+                                                        const uint32_t* __restrict__ be, uint32_t N, uint32_t kblk,
+                                                        Fr* __restrict__ partial) {
+    const uint32_t c = blockIdx.x / kblk;
+    const uint32_t k = (blockIdx.x % kblk) * blockDim.x + threadIdx.x;
+    if (k >= N) return;
+    const uint32_t W = N >> 5, kw = k >> 5, below = (1u << (k & 31)) - 1u;
+    const uint32_t u0 = be[2 * c], cnt = be[2 * c + 1] - u0;
+    f29<P29> total = zero29<P29>();
+    for (uint32_t h = 0; h < cnt; h += MP_SP_LZ) {
+        const uint32_t nq = min(cnt - h, MP_SP_LZ);
+        uint4 v[MP_SP_LZ][2];
+        uint32_t qi[MP_SP_LZ];
+        int have = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < MP_SP_LZ; j++) {
+            qi[j] = j < nq ? order[u0 + h + j] : 0u;
+            v[j][0] = v[j][1] = make_uint4(0, 0, 0, 0);
+            if (j < nq) {
+                const uint32_t* d = desc + (size_t)q_row[qi[j]] * (2 * W);
+                const uint32_t word = d[kw];
+                if ((word >> (k & 31)) & 1u) {
+                    const uint32_t s = srcs[d[W + kw] + __popc(word & below)];
+                    const uint4* src = reinterpret_cast<const uint4*>(
+                        (s & MP_SRC_AUX) ? aux + 4 * (size_t)(s & ~MP_SRC_AUX) : item + 4 * (size_t)s);
+                    v[j][0] = src[0];
+                    v[j][1] = src[1];
+                    have = 1;
+                }
+            }
+        }
+        if (!__any(have)) continue;  // (the same for every lane of the wave)
+        const f29<P29> r = mp_block<MP_SP_LZ>(v, qi, nq, rp);
+        total = csub29<P29>(carry29<P29>(add29_raw<P29>(total, r)));
+    }
+    total = csub29<P29>(carry29<P29>(total));
+    pack29<P29>(total, partial[(size_t)c * N + k].v);
+}
+
+// the rows' descriptors, checked (every index a kernel will follow is validated here) and uploaded
+// with the source list, the queries' rows and the literal values
+struct MpSparseUp {
+    uvec<uint32_t> desc;
+    DevBuf d_desc, d_qrow, d_srcs, d_aux;
+    explicit MpSparseUp(vc_ctx* ctx) : d_desc(ctx), d_qrow(ctx), d_srcs(ctx), d_aux(ctx) {}
+};
+static int mp_sparse_upload(vc_ctx* ctx, size_t N, size_t Q, const MpSparse& sp, MpSparseUp* up) {
+    const size_t W = N / 32, R = sp.n_rows;
+    if (N % 32 || R >= MP_SRC_AUX || Q >= MP_SRC_AUX) return VC_E_RANGE;
+    const size_t nnz = R ? sp.row_ptr[R] : 0;
+    up->desc.assign(R * 2 * W, 0);
+    for (size_t d = 0; d < R; d++) {
+        uint32_t* bm = &up->desc[d * 2 * W];
+        const uint32_t a = sp.row_ptr[d], b = sp.row_ptr[d + 1];
+        if (a > b || b > nnz) return VC_E_INVALID;
+        for (uint32_t e = a; e < b; e++) {
+            const uint32_t col = sp.col[e], s = sp.src[e];
+            if (col >= N || (e > a && col <= sp.col[e - 1])) return VC_E_INVALID;  // ascending: the rank is the index
+            if ((s & MP_SRC_AUX) ? (s & ~MP_SRC_AUX) >= sp.n_aux : s >= sp.n_item) return VC_E_INVALID;
+            bm[col >> 5] |= 1u << (col & 31);
+        }
+        uint32_t run = a;
+        for (size_t w = 0; w < W; w++) {
+            bm[W + w] = run;
+            run += (uint32_t)__builtin_popcount(bm[w]);
+        }
+    }
+    for (size_t q = 0; q < Q; q++)
+        if (sp.q_row[q] >= R) return VC_E_INVALID;
+    hipStream_t st = ctx->stream;
+    VK_TRY(up->d_desc.ensure(std::max<size_t>(up->desc.size(), 1) * 4));
+    VK_TRY(up->d_qrow.ensure(Q * 4));
+    VK_TRY(up->d_srcs.ensure(std::max<size_t>(nnz, 1) * 4));
+    VK_TRY(up->d_aux.ensure(std::max<size_t>(sp.n_aux, 1) * 32));
+    if (!up->desc.empty())
+        VK_CHECK_HIP(hipMemcpyAsync(up->d_desc.p, up->desc.data(), up->desc.size() * 4, hipMemcpyHostToDevice, st));
+    VK_CHECK_HIP(hipMemcpyAsync(up->d_qrow.p, sp.q_row, Q * 4, hipMemcpyHostToDevice, st));
+    if (nnz) VK_CHECK_HIP(hipMemcpyAsync(up->d_srcs.p, sp.src, nnz * 4, hipMemcpyHostToDevice, st));
+    if (sp.n_aux) VK_CHECK_HIP(hipMemcpyAsync(up->d_aux.p, sp.aux, sp.n_aux * 32, hipMemcpyHostToDevice, st));
+    return VC_OK;
+}
+
+int mp_prove_sparse(vc_ctx* ctx, int scheme, int table, size_t N, size_t Q, const uint64_t* com_xy,
+                    const uint8_t* com_inf, const uint64_t* z, const uint64_t* y, const MpSparse& sp, uint64_t* d_xy,
+                    uint8_t* d_inf, vc_ipa_proof* ipa_proof, uint64_t* kzg_xy, uint8_t* kzg_inf, uint64_t* kzg_y) {
+    if (!ctx || !com_xy || !com_inf || !z || !y || !d_xy || !d_inf || ctx->curve != VC_CURVE_BN254 || !is_pow2(N) ||
+        Q == 0 || !sp.q_row || (sp.n_rows && (!sp.row_ptr || !sp.col || !sp.src)) || (sp.n_aux && !sp.aux) ||
+        (sp.n_item && !sp.d_item))
+        return VC_E_INVALID;
+    if (scheme == 0 ? !proof_ok(ipa_proof) : (scheme != 1 || !kzg_xy || !kzg_inf || !kzg_y)) return VC_E_INVALID;
+    Guard g(ctx);
+    Table* t = ctx->table(table);
+    if (!t) return VC_E_TABLE;
+    std::vector<uint32_t> zval;
+    VK_TRY(mp_points(N, Q, z, &zval));
+    const size_t Z = zval.size();
+    hipStream_t st = ctx->stream;
+    MpPlan pl(ctx);
+    MpSparseUp up(ctx);
+    DevBuf d_S(ctx);
+    vc_transcript* tr = nullptr;
+    Fr r;
+    int s = mp_begin_overlapped(N, Q, com_xy, com_inf, z, y, &tr, &r, [&]() -> int {
+        VK_TRY(d_S.ensure(Z * N * 32));
+        VK_TRY(mp_sparse_upload(ctx, N, Q, sp, &up));
+        return mp_plan(ctx, N, Q, z, 0, zval, &pl);
+    });
+    if (s != VC_OK) {
+        (void)hipStreamSynchronize(st);  // uploads from the plan's vectors may be queued
+        return s;
+    }
+    auto run = [&]() -> int {
+        const uint32_t kblk = (uint32_t)((N + 255) / 256);
+        VK_LAUNCH(ctx, "mp_rpow", k_mp_rpow, (Q + 255) / 256, 256, 0, r, (size_t)0, Q, pl.d_rp.as<uint32_t>());
+        VK_LAUNCH(ctx, "mp_sparse_chunk", k_mp_sparse_chunk, (size_t)pl.nch * kblk, 256, 0, up.d_desc.as<uint32_t>(),
+                  up.d_qrow.as<uint32_t>(), up.d_srcs.as<uint32_t>(), sp.d_item, up.d_aux.as<uint64_t>(),
+                  pl.d_rp.as<uint32_t>(), pl.d_order.as<uint32_t>(), pl.d_be.as<uint32_t>(), (uint32_t)N, kblk,
+                  pl.d_part.as<Fr>());
+        VK_LAUNCH(ctx, "mp_chunk_reduce", k_mp_chunk_reduce, Z * kblk, 256, 0, pl.d_part.as<Fr>(), pl.d_zc.as<uint32_t>(),
+                  N, kblk, d_S.as<Fr>());
+        return mp_finish(ctx, scheme, t, N, zval, d_S.p, 1, tr, d_xy, d_inf, ipa_proof, kzg_xy, kzg_inf, kzg_y);
+    };
+    s = run();
+    if (s != VC_OK) (void)hipStreamSynchronize(st);
+    vc_transcript_free(tr);
+    return s;
+}
+
 // P independent multiproofs of Q queries each (same N, one CRS / SRS) on one GPU, proof-parallel:
 // the host transcripts (records + serial SHA-256, the part that bounds one proof) run on worker
 // threads while the GPU accumulates every proof whose challenge r is ready; each later stage then

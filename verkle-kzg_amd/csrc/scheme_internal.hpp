@@ -31,4 +31,30 @@ int mp_begin_accumulate(vc_ctx* ctx, size_t N, size_t Q, const uint64_t* com_xy,
                         const uint64_t* z, const uint64_t* y, size_t first, size_t Qs, const void* d_data, void* d_S,
                         vc_transcript** tr_out, uint64_t* r_out);
 
+// A multiproof whose evaluation rows are sparse and already (mostly) on the device -- the verkle
+// tree proofs (verkle.cpp): the per-point sums S[row(z_i)][k] += r^i f_i[k] are accumulated from the
+// rows' non-zeros instead of Q x N dense evaluations. The n_rows distinct rows are given in CSR
+// form: row d's non-zeros are [row_ptr[d], row_ptr[d + 1]) of col / src, columns strictly ascending;
+// src s means the canonical Fr value d_item[4 s] (s < n_item; device memory) or, with MP_SRC_AUX
+// set, aux[4 (s & ~MP_SRC_AUX)] (aux: n_aux host values, uploaded). Query i opens row q_row[i]
+// (many queries may share a row). The transcript over all (C, z, y) runs on a helper thread while
+// the rows' descriptors and the queries' plan are built and uploaded; then r's powers, the sums,
+// and mp_finish (G = 1). The proof equals vc_multiproof_prove's for the same queries with the rows
+// written out densely. N must be a multiple of 32.
+constexpr uint32_t MP_SRC_AUX = 0x80000000u;
+struct MpSparse {
+    size_t n_rows = 0;
+    const uint32_t* row_ptr = nullptr;  // n_rows + 1
+    const uint32_t* col = nullptr;
+    const uint32_t* src = nullptr;
+    const uint32_t* q_row = nullptr;    // Q
+    const uint64_t* d_item = nullptr;   // device, n_item x 4 u64
+    size_t n_item = 0;
+    const uint64_t* aux = nullptr;  // host, n_aux x 4 u64
+    size_t n_aux = 0;
+};
+int mp_prove_sparse(vc_ctx* ctx, int scheme, int table, size_t N, size_t Q, const uint64_t* com_xy,
+                    const uint8_t* com_inf, const uint64_t* z, const uint64_t* y, const MpSparse& sp, uint64_t* d_xy,
+                    uint8_t* d_inf, vc_ipa_proof* ipa_proof, uint64_t* kzg_xy, uint8_t* kzg_inf, uint64_t* kzg_y);
+
 }  // namespace vk

@@ -53,6 +53,11 @@ SIGNATURES = {
     "vc_verkle_debug_nodes": (c_int, [c_void_p, c_size_t, P, P, P, P]),
     "vc_verkle_debug_ext_stage": (c_int, [c_void_p, c_int, P]),
     "vc_verkle_stats": (c_int, [c_void_p, P, P, P]),
+    "vc_verkle_proof_size": (c_int, [c_void_p, P, c_size_t, P, P]),
+    "vc_verkle_prove": (c_int, [c_void_p, c_int, c_int, c_void_p, P, c_size_t, P, P, P]),
+    "vc_verkle_verify": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, P, ctypes.c_uint8, P, P, c_size_t, P,
+                                 ctypes.POINTER(c_int)]),
+    "vc_verkle_proof_queries": (c_int, [c_void_p, c_int, c_void_p, P, c_size_t, c_size_t, P, P, P, P, P, P]),
     "vc_transcript_reserve": (None, [c_void_p, c_size_t]),
     "vc_msm_windows": (c_int, [c_int, c_size_t, P, P, P]),
     "vc_msm_last_plan": (c_int, [c_void_p, P, P, P, P, P]),
