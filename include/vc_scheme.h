@@ -2,12 +2,15 @@
  * operations (/root/reference/vector-commit/src/lib.rs:70-174) for BN254 G1, with every
  * MSM / quotient / fold on the GPU and the serial Fiat-Shamir work on the host.  KZG openings
  * are verified with the BN254 pairing: one at a time on the host (vc_kzg_verify), or a batch on
- * the GPU with one verdict per proof (vc_kzg_verify_many).
+ * the GPU with one verdict per proof (vc_kzg_verify_many); IPA openings likewise, one at a time
+ * (vc_ipa_verify) or a batch with one verdict each (vc_ipa_verify_many).
  *
  * Field elements (Fr) are 4 canonical little-endian u64 limbs; points are canonical affine
  * x[4], y[4] + a u8 identity flag (as in vc_msm.h).  All calls are synchronous and return
- * VC_OK or a VC_E_* status (vc_msm.h).  The reference's `todo!()` batch methods
- * (prove_batch / verify_batch, ipa/mod.rs:156-189, kzg/mod.rs:156-197) have no counterpart.
+ * VC_OK or a VC_E_* status (vc_msm.h).  The reference leaves its batch methods `todo!()`
+ * (prove_batch / verify_batch, ipa/mod.rs:156-189, kzg/mod.rs:156-197); here vc_ipa_prove takes a
+ * batch, and vc_ipa_verify_many / vc_kzg_verify_many verify n independent openings with one verdict
+ * each (what verify_batch would return per entry; no aggregated single-verdict check).
  *
  * Scope: the protocol layer is instantiated for BN254 (the only curve the reference runs,
  * vector-commit/Cargo.toml:15).  The MSM / commit engines (vc_msm.h) also serve BLS12-381 G1
@@ -83,6 +86,28 @@ int vc_ipa_prove(vc_ctx* ctx, int table, size_t N, const uint64_t* data, const u
 int vc_ipa_verify(vc_ctx* ctx, int table, size_t N, const uint64_t* com_xy, uint8_t com_inf,
                   const uint64_t* point, const vc_ipa_proof* proof, vc_transcript* transcript,
                   int* result);
+/* n independent openings (same N, one CRS), one verdict each: results[i] = 1 / 0 as
+ * low_level_verify_ipa (ipa/mod.rs:321-360) of entry i. Flat layouts, K = log2 N rounds:
+ * com_xy n x 8, com_inf n, points n x 4, l_xy / r_xy n x K x 8, l_inf / r_inf n x K,
+ * tip n x 4, y n x 4 (u64, canonical). transcripts: NULL, or n handles, each NULL (fresh
+ * "ipa") or a prior state, advanced as vc_ipa_verify advances it.
+ * For every entry vc_ipa_verify answers with VC_OK, results[i] is its result. Malformed proof
+ * contents give the verdict 0 and VC_OK, as in vc_kzg_verify_many and unlike vc_ipa_verify (which
+ * returns VC_E_NOT_ON_CURVE for an off-curve L_k): a coordinate of C, L_k or R_k >= p, such a point
+ * off the curve, tip, y or point >= r; no entry changes another's verdict, and the identity flag
+ * is a valid input for C, L_k and R_k. A point that is a domain element w^i not below N as an
+ * integer is the verifier's own input, not proof content: VC_E_DOMAIN for the whole call before
+ * any GPU work, nothing written to results (as vc_ipa_prove treats a batch). VC_E_INVALID: N not a
+ * power of two or < 2, a table of fewer than N + 1 points, a context that is not BN254, null
+ * arrays with n > 0. n = 0 is VC_OK.
+ * The transcripts run on the host pool, everything else on the device (scalar rows, the fixed-base
+ * commit of the rows, the per-proof sum over C, L_k, R_k and the verdict), in chunks of at most
+ * 16384 proofs: the device workspace does not grow with n. Throughput-shaped: a batch of one pays
+ * the whole pipeline's launches and is slower than vc_ipa_verify. */
+int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n,
+                       const uint64_t* com_xy, const uint8_t* com_inf, const uint64_t* points,
+                       const uint64_t* l_xy, const uint8_t* l_inf, const uint64_t* r_xy, const uint8_t* r_inf,
+                       const uint64_t* tip, const uint64_t* y, vc_transcript** transcripts, uint8_t* results);
 /* prove_commitment (:199-234): proof of knowledge of the first n = data.max() + 1 values
  * behind a commitment (L, R per round, tip; y is set to 0). n must be a power of two: the
  * reference's assert in vec_add_and_distribute (utils.rs:37) panics on any odd split above 1

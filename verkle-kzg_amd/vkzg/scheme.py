@@ -51,6 +51,17 @@ def _pt_arrays(pts):
     return xy, inf
 
 
+def _pt_arrays_many(pts):
+    """_pt_arrays for long lists (verify_many: n x (1 + 2 log2 N) points): one join over the
+    coordinates' bytes, no per-point buffer assignment"""
+    n = len(pts)
+    zero = bytes(64)
+    buf = b"".join(zero if P is None else (int(P[0]) & _M256).to_bytes(32, "little") + (int(P[1]) & _M256).to_bytes(32, "little")
+                   for P in pts)
+    inf = np.fromiter((P is None for P in pts), dtype=np.uint8, count=n)
+    return np.frombuffer(buf, dtype="<u8").reshape(n, 8).astype(np.uint64), inf
+
+
 def _pt(xy, inf):
     if inf:
         return None
@@ -272,6 +283,37 @@ class IPA:
 
     def verify(self, commitment, index, proof):
         return self.verify_point(commitment, index, proof)
+
+    def _verify_many_arrays(self, commitments, points, proofs):
+        """vc_ipa_verify_many's flat arrays (com_xy, com_inf, points, l_xy, l_inf, r_xy, r_inf, tip, y)
+        and which proofs have log2 N rounds (the others go in as identities and are rejected by the
+        caller). Values as given (low 256 bits): a malformed entry must reach the library unreduced."""
+        K = _log2(self.N)
+        good = [len(pr.l) == K and len(pr.r) == K for pr in proofs]
+        none = [None] * K
+        cxy, cinf = _pt_arrays_many(commitments)
+        lxy, linf = _pt_arrays_many([P for pr, g in zip(proofs, good) for P in (pr.l if g else none)])
+        rxy, rinf = _pt_arrays_many([P for pr, g in zip(proofs, good) for P in (pr.r if g else none)])
+        pts = ints_to_limbs([int(p) & _M256 for p in points], 4)
+        tips = ints_to_limbs([int(pr.tip) & _M256 for pr in proofs], 4)
+        ys = ints_to_limbs([int(pr.y) & _M256 for pr in proofs], 4)
+        return (cxy, cinf, pts, lxy, linf, rxy, rinf, tips, ys), good
+
+    def verify_many(self, commitments, points, proofs, transcripts=None):
+        """n openings on the GPU, one verdict each (vc_ipa_verify_many) -> list of bool; transcripts:
+        None, or one TranscriptHasher (a prior state, advanced) or None per opening. VCError
+        (VC_E_DOMAIN) when a point is a domain element that is not below N."""
+        n = len(proofs)
+        if n == 0:
+            return []
+        arrs, good = self._verify_many_arrays(commitments, points, proofs)
+        trs = None
+        if transcripts is not None and any(t is not None for t in transcripts):
+            trs = (_P * n)(*[(t.h if t is not None else None) for t in transcripts])
+        out = np.zeros(n, dtype=np.uint8)
+        check(lib().vc_ipa_verify_many(self.engine.h, self.table, self.N, n, *[_p(a) for a in arrs],
+                                       ctypes.cast(trs, _P) if trs is not None else None, _p(out)), "ipa_verify_many")
+        return [bool(v) and g for v, g in zip(out, good)]
 
     def prove_commitment(self, commitment, data):
         """:199-234 -> IPAProof with l, r, tip (y = 0)."""
