@@ -10,7 +10,8 @@
  * VC_OK or a VC_E_* status (vc_msm.h).  The reference leaves its batch methods `todo!()`
  * (prove_batch / verify_batch, ipa/mod.rs:156-189, kzg/mod.rs:156-197); here vc_ipa_prove takes a
  * batch, and vc_ipa_verify_many / vc_kzg_verify_many verify n independent openings with one verdict
- * each (what verify_batch would return per entry; no aggregated single-verdict check).
+ * each (what verify_batch would return per entry); vc_kzg_verify_batch is the aggregated
+ * single-verdict check for KZG (IPA has none).
  *
  * Scope: the protocol layer is instantiated for BN254 (the only curve the reference runs,
  * vector-commit/Cargo.toml:15).  The MSM / commit engines (vc_msm.h) also serve BLS12-381 G1
@@ -224,8 +225,9 @@ int vc_multiproof_kzg_claim(vc_ctx* ctx, size_t N, size_t Q, const uint64_t* com
  * point < size and the point itself otherwise (the reference's `<` at :172).
  * A malformed key is VC_E_INVALID. A malformed proof entry -- a G1 point off the curve, a
  * coordinate >= p, an Fr value >= r -- gives the verdict 0 and VC_OK. The identity is a valid G1
- * input. Every call except vc_kzg_verify_many and vc_multiproof_verify_kzg is host code that
- * needs no context and no GPU. */
+ * input. Every call except vc_kzg_verify_many, vc_multiproof_verify_kzg and the device path
+ * of vc_kzg_batch_fold / vc_kzg_verify_batch (ctx != NULL) is host code that needs no context and
+ * no GPU. */
 typedef struct vc_kzg_vk vc_kzg_vk;
 /* [secret]_2 = secret * H, what KZG::setup computes at kzg/mod.rs:122 (H: the G2 generator) */
 int vc_kzg_g2_from_secret(const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf);
@@ -247,6 +249,35 @@ int vc_bn254_pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_in
 int vc_kzg_verify_many(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint64_t* com_xy, const uint8_t* com_inf,
                        const uint64_t* points, const uint64_t* proof_xy, const uint8_t* proof_inf,
                        const uint64_t* y, uint8_t* results);
+/* One combined check for n openings ("are all of these valid?"; the reference names it
+ * verify_batch, kzg/mod.rs:190-196, and leaves it todo!()). With one challenge rho and the
+ * weights rho^i (i = 0 .. n-1), p_i as in the check above:
+ *   P1 = sum rho^i pi_i,  P2 = (sum rho^i y_i) G - sum rho^i C_i - sum (rho^i p_i) pi_i,
+ *   accept  <=>  e(P1, [s]_2) e(P2, H) == 1.
+ * A batch of valid entries is accepted for every rho; a batch with an invalid entry is accepted
+ * for at most n - 1 of the r values of rho. rho = vc_hash_to_field(seed, 32, dst =
+ * "vkzg-kzg-batch"): the verifier draws the seed itself once it holds the inputs (no hash over the
+ * inputs); a given seed makes the call deterministic. Layouts are vc_kzg_verify_many's. */
+/* rho for a seed (host, no context) */
+int vc_kzg_batch_challenge(const uint8_t seed[32], uint64_t* rho_fr);
+/* the fold alone: P1, P2 as canonical affine points. *malformed = 1 (points unspecified) when any entry
+ * is malformed in vc_kzg_verify_many's sense: a coordinate >= p, a point off the curve, y or point >= r.
+ * ctx == NULL: host path (host pool), any n.  ctx != NULL: device path, BN254 context.
+ * VC_E_INVALID: a null key, a context that is not BN254, null arrays with n > 0, rho_fr >= r. */
+int vc_kzg_batch_fold(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint64_t* com_xy, const uint8_t* com_inf,
+                      const uint64_t* points, const uint64_t* proof_xy, const uint8_t* proof_inf, const uint64_t* y,
+                      const uint64_t* rho_fr, uint64_t* p1_xy, uint8_t* p1_inf, uint64_t* p2_xy, uint8_t* p2_inf,
+                      int* malformed);
+/* *result = 1 when the combined check accepts, else 0. seed == NULL: 32 bytes of OS entropy (getrandom).
+ * results: NULL, or n bytes. When the combined check accepts they are all 1 and no per-opening pairing
+ * runs. When it rejects (a malformed entry included) they are vc_kzg_verify_many's verdicts, so ctx is
+ * required (VC_E_INVALID with ctx == NULL and results != NULL). n = 0: VC_OK, *result = 1.
+ * A malformed proof entry gives *result = 0 with VC_OK; the identity flag is a valid input for C_i
+ * and pi_i. The device path works in chunks of at most 2^20 entries: its workspace does not grow
+ * with n. */
+int vc_kzg_verify_batch(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint64_t* com_xy, const uint8_t* com_inf,
+                        const uint64_t* points, const uint64_t* proof_xy, const uint8_t* proof_inf, const uint64_t* y,
+                        const uint8_t* seed32, int* result, uint8_t* results);
 /* verify_multiproof for KZG (multiproof.rs:178-215): vc_multiproof_kzg_claim's computation,
  * then vc_kzg_verify of (E - D, t, inner proof) */
 int vc_multiproof_verify_kzg(vc_ctx* ctx, const vc_kzg_vk* vk, size_t N, size_t Q, const uint64_t* com_xy,

@@ -165,6 +165,25 @@ __global__ void k_random(uint64_t seed, uint32_t n, int sbits, typename C::Aff* 
 }
 
 // ------------------------------------------------------------------ host entry points
+// t as an n-point table whose bases a kernel of the caller writes (Montgomery affine + identity
+// flags, what k_upload writes): everything derived from the old bases is dropped
+template <class C>
+static int reserve_t(vc_ctx* ctx, Table* t, size_t n) {
+    using Aff = typename C::Aff;
+    t->curve = ctx->curve;
+    t->n = n;
+    t->fb_c = t->fb_W = 0;
+    t->fb_auto = false;
+    t->fb.release();
+    delete t->lead;
+    t->lead = nullptr;
+    t->lead_k = t->lead_c = 0;
+    t->subgroup = -1;
+    t->fast_ok = t->phi_ok = t->win_ok = 0;
+    VK_TRY(t->bases.ensure(std::max<size_t>(n, 1) * sizeof(Aff)));
+    return t->inf.ensure(std::max<size_t>(n, 1));
+}
+
 template <class C>
 static int fill_t(vc_ctx* ctx, Table* t, const uint64_t* xy, const uint8_t* inf, size_t n) {
     using Aff = typename C::Aff;
@@ -217,6 +236,15 @@ int bases_fill(vc_ctx* ctx, Table* t, const uint64_t* xy, const uint8_t* inf, si
         case VC_CURVE_BN254: return fill_t<BN254G1>(ctx, t, xy, inf, n);
         case VC_CURVE_BLS12_381: return fill_t<BLS381G1>(ctx, t, xy, inf, n);
         case VC_CURVE_BANDERSNATCH: return fill_t<Bandersnatch>(ctx, t, xy, inf, n);
+    }
+    return VC_E_INVALID;
+}
+
+int bases_reserve(vc_ctx* ctx, Table* t, size_t n) {
+    switch (ctx->curve) {
+        case VC_CURVE_BN254: return reserve_t<BN254G1>(ctx, t, n);
+        case VC_CURVE_BLS12_381: return reserve_t<BLS381G1>(ctx, t, n);
+        case VC_CURVE_BANDERSNATCH: return reserve_t<Bandersnatch>(ctx, t, n);
     }
     return VC_E_INVALID;
 }

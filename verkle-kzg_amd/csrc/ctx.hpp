@@ -350,6 +350,9 @@ int point_words(int curve);
 int aff_limbs64(int curve);  // NL of the base field in u64 limbs
 int bases_upload(vc_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t n, int* id);
 int bases_fill(vc_ctx* ctx, Table* t, const uint64_t* xy, const uint8_t* inf, size_t n);
+// t as an n-point table whose bases (t->bases: Montgomery affine, t->inf) the caller's own kernel
+// writes on ctx->stream, as bases_fill's upload kernel would; no check, nothing uploaded
+int bases_reserve(vc_ctx* ctx, Table* t, size_t n);
 int bases_random(vc_ctx* ctx, uint64_t seed, size_t n, int* id);
 int bases_download(vc_ctx* ctx, Table* t, uint64_t* xy, uint8_t* inf);
 int fixed_base_precompute(vc_ctx* ctx, Table* t, int c, int windows = 0);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/vc_scheme.h"
+#include "kzg_batch.hpp"
 #include "pairing_internal.hpp"
 
 using namespace vk;
@@ -42,6 +43,10 @@ bool fr_words(const uint64_t* fr, uint32_t* w) {  // canonical words; false when
 }
 
 }  // namespace
+
+bool vk::kzg_pair_check(const vc_kzg_vk* vk, const G1A& P1, const G1A& P2) {
+    return kzgb::pair_check(P1, P2, vk->lines, vk->lines + PC::ATE_LINES);
+}
 
 extern "C" {
 

@@ -16,3 +16,10 @@ struct vc_kzg_vk {
     // Miller-loop lines of [s]_2, then of H
     vk::bn::LineCoef lines[2 * vk::bn::PC::ATE_LINES];
 };
+
+namespace vk {
+// e(P1, [s]_2) e(P2, H) == 1 over the key's tables for two points of G1 as accumulators, the
+// identity included (pairing_host.cpp; the batch verifier's final check: vc_kzg_verify's inputs
+// cannot express it)
+bool kzg_pair_check(const vc_kzg_vk* vk, const bn::G1A& P1, const bn::G1A& P2);
+}  // namespace vk

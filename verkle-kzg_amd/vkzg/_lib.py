@@ -117,6 +117,10 @@ SIGNATURES = {
     "vc_kzg_verify": (c_int, [c_void_p, P, ctypes.c_uint8, P, P, ctypes.c_uint8, P, ctypes.POINTER(c_int)]),
     "vc_bn254_pairing_check": (c_int, [c_size_t, P, P, P, P, ctypes.POINTER(c_int)]),
     "vc_kzg_verify_many": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P]),
+    "vc_kzg_batch_challenge": (c_int, [P, P]),
+    "vc_kzg_batch_fold": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P, P, P, P, P,
+                                  ctypes.POINTER(c_int)]),
+    "vc_kzg_verify_batch": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P, ctypes.POINTER(c_int), P]),
     "vc_multiproof_verify_kzg": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, P, P, P, P, P, ctypes.c_uint8, P,
                                          ctypes.c_uint8, P, ctypes.POINTER(c_int)]),
     # vc_comm.h

@@ -386,7 +386,8 @@ def pairing_check(pairs):
 
 class KZGVerifyingKey:
     """[s]_2 and the domain size: all KZG::verify_point needs (no SRS, no secret). Host code
-    except verify_many, which takes an Engine. VCError(VC_E_INVALID) for a malformed [s]_2."""
+    except verify_many, and verify_batch / batch_fold when given an Engine. VCError(VC_E_INVALID)
+    for a malformed [s]_2."""
 
     def __init__(self, g2, size):
         xy, inf = _g2_array(g2)
@@ -425,6 +426,59 @@ class KZGVerifyingKey:
         check(lib().vc_kzg_verify_many(engine.h, self.h, n, _p(cxy), _p(cinf), _p(pts), _p(pxy), _p(pinf), _p(ys),
                                        _p(out)), "kzg_verify_many")
         return [bool(v) for v in out]
+
+    def _batch_arrays(self, commitments, points, proofs):
+        cxy, cinf = _pt_arrays(commitments)
+        pxy, pinf = _pt_arrays([pr["proof"] for pr in proofs])
+        pts = ints_to_limbs([int(p) & _M256 for p in points], 4)
+        ys = ints_to_limbs([int(pr["y"]) & _M256 for pr in proofs], 4)
+        return cxy, cinf, pts, pxy, pinf, ys
+
+    def batch_fold(self, engine, commitments, points, proofs, rho):
+        """The fold of vc_kzg_verify_batch alone (vc_kzg_batch_fold): (P1, P2) for the challenge rho,
+        or None when an entry is malformed. engine None: the host path."""
+        n = len(proofs)
+        a = self._batch_arrays(commitments, points, proofs) if n else (None,) * 6
+        ptr = [_p(x) if x is not None else None for x in a]
+        out = np.zeros((2, 8), dtype=np.uint64)
+        inf = np.zeros(2, dtype=np.uint8)
+        bad = ctypes.c_int()
+        check(lib().vc_kzg_batch_fold(engine.h if engine is not None else None, self.h, n, *ptr, _p(_fr_raw(rho)),
+                                      _p(out[0]), _p(inf[0:1]), _p(out[1]), _p(inf[1:2]), ctypes.byref(bad)),
+              "kzg_batch_fold")
+        if bad.value:
+            return None
+        return _pt(out[0], inf[0]), _pt(out[1], inf[1])
+
+    def verify_batch(self, engine, commitments, points, proofs, seed=None, locate=False):
+        """One combined check for n openings (vc_kzg_verify_batch) -> bool: are all of them valid?
+        seed: 32 bytes the verifier draws after it holds the inputs (None: OS entropy). locate=True
+        (needs an Engine) -> (bool, list of bool): when the combined check rejects, the per-opening
+        verdicts of verify_many say which ones are bad. engine None: the host path."""
+        n = len(proofs)
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        a = self._batch_arrays(commitments, points, proofs) if n else (None,) * 6
+        ptr = [_p(x) if x is not None else None for x in a]
+        s = np.frombuffer(bytes(seed), dtype=np.uint8).copy() if seed is not None else None
+        out = np.zeros(max(n, 1), dtype=np.uint8) if locate else None
+        res = ctypes.c_int()
+        check(lib().vc_kzg_verify_batch(engine.h if engine is not None else None, self.h, n, *ptr,
+                                        _p(s) if s is not None else None, ctypes.byref(res),
+                                        _p(out) if locate else None), "kzg_verify_batch")
+        if locate:
+            return bool(res.value), [bool(v) for v in out[:n]]
+        return bool(res.value)
+
+
+def kzg_batch_challenge(seed):
+    """rho of vc_kzg_verify_batch for a 32-byte seed: hash_to_field(seed, b"vkzg-kzg-batch")."""
+    if len(seed) != 32:
+        raise ValueError("seed: 32 bytes")
+    s = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+    out = np.zeros(4, dtype=np.uint64)
+    check(lib().vc_kzg_batch_challenge(_p(s), _p(out)), "kzg_batch_challenge")
+    return limbs_to_int(out)
 
 
 class KZG:
@@ -496,6 +550,10 @@ class KZG:
     def verify_many(self, commitments, points, proofs):
         """One verdict per opening, the batch on the GPU (test_amortized_proof's loop)."""
         return self.verifying_key().verify_many(self.engine, commitments, points, proofs)
+
+    def verify_batch(self, commitments, points, proofs, seed=None, locate=False):
+        """One verdict for the whole batch (KZGVerifyingKey.verify_batch on this engine)."""
+        return self.verifying_key().verify_batch(self.engine, commitments, points, proofs, seed=seed, locate=locate)
 
     def quotient(self, point, data):
         ev = data.limbs()
