@@ -210,16 +210,9 @@ void vc_ctx::collect_timers() {
     pending.clear();
 }
 
-namespace {
+using vk::Guard;
 
-struct Guard {
-    vc_ctx* c;
-    std::lock_guard<std::recursive_mutex> lk;
-    explicit Guard(vc_ctx* ctx) : c(ctx), lk(ctx->mu) { (void)hipSetDevice(ctx->device); }
-    ~Guard() {
-        if (c->timing) c->collect_timers();
-    }
-};
+namespace {
 
 bool valid_curve(int c) { return c == VC_CURVE_BN254 || c == VC_CURVE_BLS12_381 || c == VC_CURVE_BANDERSNATCH; }
 
@@ -305,7 +298,6 @@ void vc_ctx_destroy(vc_ctx* ctx) {
         ctx->pin_mp.release();
         ctx->pin_ipa.release();
         ctx->pin_verkle.release();
-        ctx->pin_verkle2.release();
         for (auto& b : ctx->pin_verkle_lv) b.release();
         ctx->pin_norm_vk.release();
         ctx->pin_sparse_ck.release();
@@ -477,12 +469,10 @@ int vc_msm_device(vc_ctx* ctx, int id, size_t offset, const void* d_sc, size_t n
     Guard g(ctx);
     std::vector<uint32_t> acc(vk::point_words(ctx->curve));
     VK_TRY(msm_device_acc(ctx, id, offset, d_sc, n, mont, acc.data()));
-    static const bool timing = getenv("VKZG_HOST_TIMING") && atoi(getenv("VKZG_HOST_TIMING")) != 0;
-    if (!timing) return vk::acc_to_affine(ctx->curve, acc.data(), out_xy, out_inf);
-    const auto a0 = std::chrono::steady_clock::now();
+    if (!vk::host_timing()) return vk::acc_to_affine(ctx->curve, acc.data(), out_xy, out_inf);
+    const double a0 = vk::clock_us();
     const int st = vk::acc_to_affine(ctx->curve, acc.data(), out_xy, out_inf);
-    fprintf(stderr, "msm_affine_us=%.1f\n",
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a0).count());
+    fprintf(stderr, "msm_affine_us=%.1f\n", vk::clock_us() - a0);
     return st;
 }
 

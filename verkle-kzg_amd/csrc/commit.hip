@@ -285,39 +285,30 @@ __global__ void __launch_bounds__(256) k_norm_prep_vk(BN254G1::Acc* __restrict__
     const uint32_t tid = threadIdx.x, nb = gridDim.x;
     const uint64_t tag = (uint64_t)epoch << 32;
     if (tid == 0) {
-        if (tags) {
-            const fe<F> mine = tot[blockIdx.x];  // (this thread's own store in norm_prep_block)
+        const fe<F> mine = tot[blockIdx.x];  // (this thread's own store in norm_prep_block)
 #pragma unroll
-            for (int k = 0; k < F::N; k++)
-                __hip_atomic_store(&tags[(size_t)F::N * blockIdx.x + k], tag | mine.v[k], __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            __threadfence();  // this block's product before its arrival
-        }
+        for (int k = 0; k < F::N; k++)
+            __hip_atomic_store(&tags[(size_t)F::N * blockIdx.x + k], tag | mine.v[k], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
         s_last = atomicAdd(counter, 1u) == nb - 1 ? 1u : 0u;
     }
     __syncthreads();
     if (!s_last) return;
-    if (!tags) __threadfence();
-    auto load = [&](uint32_t b) {  // another block's product: through the coherent path
+    // another block's product: every block stored its words before it arrived, so the wait is
+    // short (bounded anyway)
+    auto load = [&](uint32_t b) {
         fe<F> v;
-        if (tags) {  // every block stored its words before it arrived: the wait is short (bounded anyway)
-            const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-            for (;;) {
-                bool all = true;
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        for (;;) {
+            bool all = true;
 #pragma unroll
-                for (int k = 0; k < F::N; k++) {
-                    const uint64_t w = __hip_atomic_load(&tags[(size_t)F::N * b + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    v.v[k] = (uint32_t)w;
-                    all = all && (w & 0xffffffff00000000ull) == tag;
-                }
-                if (all || __builtin_amdgcn_s_memrealtime() - t0 > 1000000ull) break;  // (10 ms)
+            for (int k = 0; k < F::N; k++) {
+                const uint64_t w = __hip_atomic_load(&tags[(size_t)F::N * b + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                v.v[k] = (uint32_t)w;
+                all = all && (w & 0xffffffff00000000ull) == tag;
             }
-            return v;
+            if (all || __builtin_amdgcn_s_memrealtime() - t0 > 1000000ull) break;  // (10 ms)
         }
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(&tot[b]);
-#pragma unroll
-        for (int k = 0; k < F::N; k++) v.v[k] = __hip_atomic_load(&src[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return v;
     };
     const uint32_t per = (nb + 255) / 256, b0 = min(tid * per, nb), b1 = min(b0 + per, nb);
@@ -413,7 +404,6 @@ struct NormGo {
     const fe<BN254Fq>* prod = nullptr;  // what the host inverts (device view of the page-locked staging)
     const fe<BN254Fq>* inv = nullptr;   // where the host writes the inverse(s)
     uint64_t limit = 0;
-    uint64_t* dbg = nullptr;  // VKZG_NORM_DEBUG: per block (start, seen or timed out, seen) on the 100 MHz clock
 };
 // (four 64-bit loads: page-locked host memory is read over PCIe uncached)
 __device__ __forceinline__ fe<BN254Fq> load_fe_sys(const fe<BN254Fq>* p) {
@@ -494,11 +484,6 @@ __global__ void __launch_bounds__(256) k_norm_finish_vk(const BN254G1::Acc* __re
                     for (int i = 0; i < F::N; i++) v.v[i] = (uint32_t)w[i];
                     have = true;
                 }
-            }
-            if (go.dbg) {
-                go.dbg[3 * blockIdx.x] = t0;
-                go.dbg[3 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-                go.dbg[3 * blockIdx.x + 2] = (seen ? 1u : 0u) | (host ? 2u : 0u);
             }
             // per block: its own inverse from the host (distinct addresses), or made here
             if (!have) v = host ? load_fe_sys(go.inv + k) : fe_inv_bin<F>(load_fe_sys(go.prod + k));
@@ -671,6 +656,17 @@ __global__ void __launch_bounds__(64) k_fb_combine_wave(const typename Fast29<C>
 constexpr int FB_WPT = 1;
 static int fb_wpt() { return FB_WPT; }
 
+// A strided base pattern of compacted rows (the IPA rounds' L / R on their N / 2 + 1 non-zero
+// bases: measured slower and removed, commit f54c503 has the callers). Every launch passes half = 0,
+// item i is base i. The argument and its select stay in the kernel: without them the BLS12-381
+// instantiation allocates 271 VGPRs + 15 AGPRs against 270 + 14 (profiles/r11/knobs/kernels.md).
+struct StrideCols {
+    uint32_t half = 0, m = 0, off_even = 0, off_odd = 0, n_main = 0, extra = 0;
+    __host__ __device__ uint32_t base(uint32_t g, uint32_t i) const {
+        return i < n_main ? (i / half) * m + ((g & 1) ? off_odd : off_even) + i % half : extra;
+    }
+};
+
 template <class C, class Fr>
 __global__ void __launch_bounds__(256) k_fb_commit_small(const FbE<C>* __restrict__ tab,
                                                         const uint8_t* __restrict__ inf, uint32_t width, FbGeom fg,
@@ -685,8 +681,6 @@ __global__ void __launch_bounds__(256) k_fb_commit_small(const FbE<C>* __restric
     const uint32_t j = blk * 256 + threadIdx.x;
     const uint32_t i = j / WG, wg = j % WG;
     typename FC::Acc fa = FC::zero();
-    // compacted rows (cols.half != 0): commit g's item i is a table base of a strided pattern
-    // (computed: a list in host memory cost a dependent PCIe read per thread, +7 us per launch)
     const uint32_t base = cols.half ? cols.base(g, i) : i;
     // the IPA rows (IpaRows): this round's coefficient of item i, folded and stored by L's window-0
     // thread for the next round -- identity bases included -- then the item's scalar
@@ -814,7 +808,6 @@ static int fb_precompute_t(vc_ctx* ctx, Table* t, int c, int windows) {
 // Fewer windows mean fewer table points per commit, hence fewer latency-path blocks and block
 // partials: the 257-point IPA CRS at c = 16 (16 windows, 17.2 GB) proves in 0.64 ms against 0.73 at
 // c = 8 (32 windows, 134 MB), the multiproof finish 0.99 against 1.15 ms (profiles/r05/fb_default_c/).
-// VKZG_FB_C_DEFAULT (read once; A/B probe) fixes c.
 template <class Fr>
 static double fb_auto_bytes(size_t n, int c) {
     const size_t W = (size_t)(Fr::BITS + 1 + c - 1) / c;
@@ -822,9 +815,7 @@ static double fb_auto_bytes(size_t n, int c) {
 }
 template <class Fr>
 static int fb_default_c(size_t n, size_t used) {
-    static const int forced = getenv("VKZG_FB_C_DEFAULT") ? atoi(getenv("VKZG_FB_C_DEFAULT")) : 0;
     static const double budget_gb = getenv("VKZG_FB_BUDGET_GB") ? atof(getenv("VKZG_FB_BUDGET_GB")) : 20.0;
-    if (forced >= 4 && forced <= 20) return forced;
     double limit = budget_gb * 1e9 - (double)used;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = std::min(limit, (double)free_b - 4e9);
@@ -836,13 +827,9 @@ static int fb_default_c(size_t n, size_t used) {
 template <class C, class Fr>
 static int fb_commit_t(vc_ctx* ctx, Table* t, size_t width, const void* d_sc, size_t batch, int mont,
                        void* d_out_xy, uint8_t* d_out_inf, uint64_t* h_out_xy, uint8_t* h_out_inf, bool* on_host,
-                       const PinBuf* pin_sc, const std::function<void()>* overlap, const StrideCols* cols,
-                       const IpaRows* ipa) {
+                       const PinBuf* pin_sc, const std::function<void()>* overlap, const IpaRows* ipa) {
     using Acc = typename C::Acc;
-    const bool with_cols = cols && cols->half;
-    if (width > t->n && !with_cols) return VC_E_RANGE;
-    if (with_cols && (size_t)cols->extra >= t->n) return VC_E_RANGE;
-    if (with_cols && cols->base(0, cols->n_main - 1) >= t->n) return VC_E_RANGE;
+    if (width > t->n) return VC_E_RANGE;
     if (t->fb_c == 0) {
         int c = fb_default_c<Fr>(t->n, ctx->fb_auto_used());
         int st = fb_precompute_t<C>(ctx, t, c, 0);
@@ -867,14 +854,13 @@ static int fb_commit_t(vc_ctx* ctx, Table* t, size_t width, const void* d_sc, si
     const int wpt = fb_wpt();
     const size_t WG = (size_t)(W + wpt - 1) / wpt;
     const bool small = items * WG <= lanes && batch <= 64;
-    if ((with_cols || ipa) && !small) return VC_E_INVALID;  // compacted / IPA rows: the latency path only
-    if (ipa && (with_cols || width != (size_t)ipa->N + 1 || batch % 2)) return VC_E_INVALID;
-    // zero-copy on the latency path (VKZG_ZERO_COPY, A/B probe: bit 0 partials, bit 1 scalars):
-    // the kernel reads host-pinned scalars and writes its block partials to fine-grained host
-    // memory over PCIe instead of a copy engine moving them before / after it
-    static const int zc = getenv("VKZG_ZERO_COPY") ? atoi(getenv("VKZG_ZERO_COPY")) : 3;
+    if (ipa && !small) return VC_E_INVALID;  // IPA rows: the latency path only
+    if (ipa && (width != (size_t)ipa->N + 1 || batch % 2)) return VC_E_INVALID;
+    // zero-copy on the latency path: the kernel reads host-pinned scalars and writes its block
+    // partials to fine-grained host memory over PCIe instead of a copy engine moving them before /
+    // after it
     if (pin_sc) {
-        if (small && (zc & 2)) {
+        if (small) {
             d_sc = pin_sc->dp;
         } else {
             VK_TRY(ctx->ws[WS_SCALARS].ensure(items * 32));
@@ -885,60 +871,46 @@ static int fb_commit_t(vc_ctx* ctx, Table* t, size_t width, const void* d_sc, si
     }
     if (small) {  // small batch: latency path
         const uint32_t bpc = (uint32_t)((width * WG + 255) / 256);
-        // VKZG_HOST_TIMING=1: launch-to-readback, host adds and normalisation on stderr (probe)
-        static const bool timing = getenv("VKZG_HOST_TIMING") && atoi(getenv("VKZG_HOST_TIMING")) != 0;
-        auto now_us = [] {
-            return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        };
-        const double t0 = timing ? now_us() : 0.0;
+        // host_timing(): launch-to-readback, host adds and normalisation on stderr
+        const bool timing = host_timing();
+        const double t0 = timing ? clock_us() : 0.0;
         const size_t part_bytes = (size_t)batch * bpc * sizeof(Acc);
         const uint32_t nblk = (uint32_t)(batch * bpc);
         // zero-copy partials: the blocks' completion flags follow them in the fine-grained buffer
-        // (VKZG_SMALL_POLL=0, read once: wait for the stream instead)
-        static const bool poll_env = !(getenv("VKZG_SMALL_POLL") && atoi(getenv("VKZG_SMALL_POLL")) == 0);
-        const bool poll = poll_env && (zc & 1);
         const size_t flag_off = (part_bytes + 63) / 64 * 64;
         VK_TRY(ctx->pin_small.ensure(flag_off + (size_t)nblk * 4));
-        if (!(zc & 1)) VK_TRY(ctx->ws[WS_PIECE].ensure(part_bytes));
-        Acc* d_part = (zc & 1) ? static_cast<Acc*>(ctx->pin_small.dp) : ctx->ws[WS_PIECE].as<Acc>();
+        Acc* d_part = static_cast<Acc*>(ctx->pin_small.dp);
         volatile uint32_t* hflags = reinterpret_cast<volatile uint32_t*>(static_cast<uint8_t*>(ctx->pin_small.p) + flag_off);
-        uint32_t* dflags = poll ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pin_small.dp) + flag_off) : nullptr;
+        uint32_t* dflags = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pin_small.dp) + flag_off);
         const uint32_t epoch = ++ctx->small_epoch == 0 ? ++ctx->small_epoch : ctx->small_epoch;  // never 0
-        if (poll)  // (fresh page-locked memory holds anything: no stale flag may match)
-            for (uint32_t b = 0; b < nblk; b++) hflags[b] = 0;
+        // (fresh page-locked memory holds anything: no stale flag may match)
+        for (uint32_t b = 0; b < nblk; b++) hflags[b] = 0;
         VK_LAUNCH(ctx, "fb_commit_small", (k_fb_commit_small<C, Fr>), batch * bpc, 256, 0, t->fb.as<FbE<C>>(),
                   t->inf.as<uint8_t>(), (uint32_t)width, fg, reinterpret_cast<const uint32_t*>(d_sc), mont,
-                  bpc, wpt, with_cols ? *cols : StrideCols{}, ipa ? *ipa : IpaRows{}, d_part, dflags, epoch);
+                  bpc, wpt, StrideCols{}, ipa ? *ipa : IpaRows{}, d_part, dflags, epoch);
         // the few block partials are added and normalised on the host: a lone GPU lane pays
         // ~10 us per serial EC add and ~160 us per field inversion, the host ~1 us / ~20 us
         // (pinned read-back; a caller that wants host results -- h_out_xy -- gets them without the
         // upload / second read-back round trip)
         const Acc* parts = ctx->pin_small.as<Acc>();
-        if (!(zc & 1))
-            VK_CHECK_HIP(hipMemcpyAsync(ctx->pin_small.p, ctx->ws[WS_PIECE].p, part_bytes, hipMemcpyDeviceToHost,
-                                        ctx->stream));
         if (overlap && *overlap) (*overlap)();
         bool seen = false;
         // the partials serially on this thread (the host pool's wake-up cost more than the ~23 us
-        // of adds of the IPA prover's 2 x 33 partials: prove 0.89 -> 1.07 ms); while polling, each
-        // block's partial is added as soon as its flag arrives, so the adds overlap the blocks
-        // that finish later. Then one batched inversion.
+        // of adds of the IPA prover's 2 x 33 partials: prove 0.89 -> 1.07 ms); each block's partial
+        // is added as soon as its flag arrives, so the adds overlap the blocks that finish later.
+        // Then one batched inversion.
         std::vector<Acc> sums(batch);
-        // VKZG_SMALL_INCR=0 (read once; A/B probe): add the partials after the last flag instead
-        static const bool incr = !(getenv("VKZG_SMALL_INCR") && atoi(getenv("VKZG_SMALL_INCR")) == 0);
-        if (poll) {  // every block's flag at this epoch: the partials are in host memory
+        {  // every block's flag at this epoch: the partials are in host memory
             std::vector<uint8_t> done(nblk, 0), have(batch, 0);
             uint32_t ndone = 0;
             const auto w0 = std::chrono::steady_clock::now();
             for (uint32_t spins = 0;; spins++) {
                 for (uint32_t b = 0; b < nblk; b++) {
                     if (done[b] || hflags[b] != epoch) continue;
-                    if (incr) {
-                        std::atomic_thread_fence(std::memory_order_acquire);
-                        const uint32_t g = b / bpc;
-                        sums[g] = have[g] ? C::add(sums[g], parts[b]) : parts[b];
-                        have[g] = 1;
-                    }
+                    std::atomic_thread_fence(std::memory_order_acquire);
+                    const uint32_t g = b / bpc;
+                    sums[g] = have[g] ? C::add(sums[g], parts[b]) : parts[b];
+                    have[g] = 1;
                     done[b] = 1;
                     ndone++;
                 }
@@ -954,9 +926,9 @@ static int fb_commit_t(vc_ctx* ctx, Table* t, size_t width, const void* d_sc, si
                 _mm_pause();
             }
         }
-        const double t1 = timing ? now_us() : 0.0;
-        if (!seen) VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        if (!seen || !incr) {
+        const double t1 = timing ? clock_us() : 0.0;
+        if (!seen) {  // the poll gave up: the stream's end, and the sums from the start
+            VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
             std::atomic_thread_fence(std::memory_order_acquire);
             for (size_t g = 0; g < batch; g++) {
                 Acc a = parts[g * bpc];
@@ -969,11 +941,11 @@ static int fb_commit_t(vc_ctx* ctx, Table* t, size_t width, const void* d_sc, si
         std::vector<uint8_t> oinf(h_out_xy ? 0 : batch);
         uint64_t* rxy = h_out_xy ? h_out_xy : oxy.data();
         uint8_t* rinf = h_out_xy ? h_out_inf : oinf.data();
-        const double t2 = timing ? now_us() : 0.0;
+        const double t2 = timing ? clock_us() : 0.0;
         VK_TRY(acc_to_affine_batch(ctx->curve, reinterpret_cast<const uint32_t*>(sums.data()), batch, rxy, rinf));
         if (timing)
             fprintf(stderr, "[fb_small] %zu x %u partials: launch..last flag (adds overlapped) %.1f us, rest %.1f us, affine %.1f us\n",
-                    batch, bpc, t1 - t0, t2 - t1, now_us() - t2);
+                    batch, bpc, t1 - t0, t2 - t1, clock_us() - t2);
         if (h_out_xy) {
             *on_host = true;
             return VC_OK;
@@ -1009,8 +981,7 @@ static int fb_commit_t(vc_ctx* ctx, Table* t, size_t width, const void* d_sc, si
     // lanes per commit: grow while there are pieces to split and the lanes fit a wave per SIMD
     uint32_t lgG = 0;
     while (lgG < 6 && (2ull << lgG) <= nch && batch * (2ull << lgG) <= 65536) lgG++;
-    static const int grp_env = getenv("VKZG_COMBINE_GROUP") ? atoi(getenv("VKZG_COMBINE_GROUP")) : 1;  // A/B probe
-    if (grp_env && lgG > 0 && lgG < 6)
+    if (lgG > 0 && lgG < 6)
         VK_LAUNCH(ctx, "fb_combine", (k_fb_combine_grp<C>), (uint32_t)(((batch << lgG) + 255) / 256), 256, 0,
                   ctx->ws[WS_PIECE].as<typename Fast29<C>::type::Acc>(), (uint32_t)nch, (uint32_t)batch, lgG,
                   ctx->ws[WS_OUT].as<Acc>());
@@ -1126,25 +1097,16 @@ int normalize_rows_items(vc_ctx* ctx, void* d_rows, size_t n, const uint32_t* ad
     // the last block's scan costs ~17 us of serial multiplies whatever nblk is; the host's trick
     // ~54 ns per block: the scan pays from ~128 blocks on (c1 / c2 rows: 88 -> 74 us of prep + gap,
     // width-4 rows 76 -> 58 us; a 256-row level 24 -> 43 us: profiles/r05/verkle/sparse_norm_vk/)
-    static const size_t scan_min = getenv("VKZG_NORM_DEVSCAN") ? (size_t)atol(getenv("VKZG_NORM_DEVSCAN")) : 128;  // A/B
-    if (scan_min != 0 && nblk >= scan_min) {
+    if (nblk >= 128) {
         // the block products scanned on the device (k_norm_prep_vk's last block): the host inverts
         // their total only; page-locked [total | its inverse | flag] in the same alternating halves
         DevBuf& dt = ctx->ws[WS_NORM_TOT];
         VK_TRY(dt.ensure(2 * nblk * sizeof(fe<F>) + nblk * F::N * 8));
         fe<F>* dtot = dt.as<fe<F>>();
-        // VKZG_NORM_TAGS=0 (read per call, A/B): a fence per block before its arrival instead
-        const char* te = getenv("VKZG_NORM_TAGS");
-        uint64_t* tags = (te && atoi(te) == 0) ? nullptr : reinterpret_cast<uint64_t*>(dtot + 2 * nblk);
+        uint64_t* tags = reinterpret_cast<uint64_t*>(dtot + 2 * nblk);
         hflags[0] = 0;
         VK_LAUNCH(ctx, "norm_prep", k_norm_prep_vk, nblk, 256, 0, static_cast<BN254G1::Acc*>(d_rows), n, add_ids,
                   add_xy, add_inf, others.as<fe<F>>(), dtot, dflags, epoch, cnt.as<uint32_t>(), dtot + nblk, dh, tags);
-        static const bool dbg_on = getenv("VKZG_NORM_DEBUG") != nullptr;
-        DevBuf dbgbuf(ctx);
-        if (early_now && dbg_on) {
-            VK_TRY(dbgbuf.ensure(nblk * 24));
-            go.dbg = dbgbuf.as<uint64_t>();
-        }
         if (early_now) {
             go.per_block = 0;
             go.prod = dh;
@@ -1152,7 +1114,6 @@ int normalize_rows_items(vc_ctx* ctx, void* d_rows, size_t n, const uint32_t* ad
             VK_LAUNCH(ctx, "norm_finish", k_norm_finish_vk, nblk, 256, 0, static_cast<const BN254G1::Acc*>(d_rows), n,
                       others.as<fe<F>>(), dtot + nblk, dst, out_xy, out_inf, out_item, (const fe<F>*)nullptr, go);
         }
-        const auto d0 = std::chrono::steady_clock::now();
         if (overlap && *overlap) (*overlap)();
         bool seen = false;
         const auto w0 = std::chrono::steady_clock::now();
@@ -1168,33 +1129,8 @@ int normalize_rows_items(vc_ctx* ctx, void* d_rows, size_t n, const uint32_t* ad
         // (queued early: this wait also covers the finish, whose blocks invert on their own past their bound)
         if (!seen) VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
         h[1] = fe_inv_bin<F>(h[0]);  // never zero: identities count as 1
-        const auto d1 = std::chrono::steady_clock::now();
-        if (early_now) release_go();
-        static const bool dbg = getenv("VKZG_NORM_DEBUG") != nullptr;
-        if (dbg)
-            fprintf(stderr, "[norm] n %zu nblk %zu early %d overlap %.1f us, flag wait + inverse %.1f us\n", n, nblk,
-                    (int)early_now, std::chrono::duration<double, std::micro>(w0 - d0).count(),
-                    std::chrono::duration<double, std::micro>(d1 - w0).count());
         if (early_now) {
-            if (go.dbg) {
-                const auto g0 = std::chrono::steady_clock::now();
-                VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-                const double sync_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - g0).count();
-                std::vector<uint64_t> hd(nblk * 3);
-                VK_CHECK_HIP(hipMemcpy(hd.data(), go.dbg, nblk * 24, hipMemcpyDeviceToHost));
-                uint64_t tmin = ~0ull, e0 = hd[1], emax = 0, smin = ~0ull, smax = 0;
-                size_t timed_out = 0;
-                for (size_t b = 0; b < nblk; b++) {
-                    tmin = std::min(tmin, hd[3 * b]);
-                    smin = std::min(smin, hd[3 * b]);
-                    smax = std::max(smax, hd[3 * b]);
-                    emax = std::max(emax, hd[3 * b + 1]);
-                    timed_out += hd[3 * b + 2] == 0;
-                }
-                fprintf(stderr, "[norm go] block 0 waited %.1f us (seen %d); starts span %.1f us; last block done waiting %.1f us after block 0; %zu timed out; host sync after go %.1f us\n",
-                        (hd[1] - hd[0]) / 100.0, (int)hd[2], (smax - smin) / 100.0, ((double)emax - (double)e0) / 100.0,
-                        timed_out, sync_us);
-            }
+            release_go();
             return VC_OK;
         }
         std::atomic_thread_fence(std::memory_order_release);  // the inverse before the launch that reads it
@@ -1360,7 +1296,7 @@ bool fb_small_path(vc_ctx* ctx, Table* t, size_t width, size_t batch) {
 
 int msm_batch_run(vc_ctx* ctx, Table* t, size_t width, const void* d_sc, size_t batch, int mont,
                   void* d_out_xy, uint8_t* d_out_inf, uint64_t* h_out_xy, uint8_t* h_out_inf, bool* on_host,
-                  const PinBuf* pin_sc, const std::function<void()>* overlap, const StrideCols* with_cols,
+                  const PinBuf* pin_sc, const std::function<void()>* overlap,
                   const IpaRows* ipa) {
     bool dummy = false;
     if (!on_host) on_host = &dummy;
@@ -1369,13 +1305,13 @@ int msm_batch_run(vc_ctx* ctx, Table* t, size_t width, const void* d_sc, size_t 
     switch (t->curve) {
         case VC_CURVE_BN254:
             return fb_commit_t<BN254G1, BN254Fr>(ctx, t, width, d_sc, batch, mont, d_out_xy, d_out_inf, h_out_xy,
-                                                 h_out_inf, on_host, pin_sc, overlap, with_cols, ipa);
+                                                 h_out_inf, on_host, pin_sc, overlap, ipa);
         case VC_CURVE_BLS12_381:
             return fb_commit_t<BLS381G1, BLS381Fr>(ctx, t, width, d_sc, batch, mont, d_out_xy, d_out_inf, h_out_xy,
-                                                   h_out_inf, on_host, pin_sc, overlap, with_cols, ipa);
+                                                   h_out_inf, on_host, pin_sc, overlap, ipa);
         case VC_CURVE_BANDERSNATCH:
             return fb_commit_t<Bandersnatch, BandFr>(ctx, t, width, d_sc, batch, mont, d_out_xy, d_out_inf, h_out_xy,
-                                                     h_out_inf, on_host, pin_sc, overlap, with_cols, ipa);
+                                                     h_out_inf, on_host, pin_sc, overlap, ipa);
     }
     return VC_E_INVALID;
 }

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <memory>
@@ -71,18 +73,6 @@ struct DevBuf {
     DevBuf& operator=(const DevBuf&) = delete;
 };
 
-// page-locked host staging (one per lane): device->host copies into pageable memory go through a
-// bounce buffer and start late (measured ~25 us before the MSM's second small read-back)
-// compacted rows of the batched commit's latency path (the IPA rounds' L / R): item i < n_main of
-// commit g is table base (i / half) m + (g odd ? off_odd : off_even) + i % half, item n_main is
-// base `extra` (half = 0: plain rows, item i is base i)
-struct StrideCols {
-    uint32_t half = 0, m = 0, off_even = 0, off_odd = 0, n_main = 0, extra = 0;
-    __host__ __device__ uint32_t base(uint32_t g, uint32_t i) const {
-        return i < n_main ? (i / half) * m + ((g & 1) ? off_odd : off_even) + i % half : extra;
-    }
-};
-
 // The IPA prover's L / R rows made inside the latency-path commit (commit.hip k_fb_commit_small)
 // instead of on the host: commit g (proof p = g / 2, L even, R odd), item i < n_main is
 // a[p][i % m - h] * coeff[i] for L when i % m >= h, a[p][i % m + h] * coeff[i] for R when i % m < h,
@@ -99,6 +89,8 @@ struct IpaRows {
     uint32_t N = 0, m = 0, h = 0, fold = 0, m_prev = 0, h_prev = 0;
 };
 
+// page-locked host staging (one per lane): device->host copies into pageable memory go through a
+// bounce buffer and start late (measured ~25 us before the MSM's second small read-back)
 struct PinBuf {
     void* p = nullptr;
     void* dp = nullptr;     // the device's address of p (kernels read / write it over PCIe)
@@ -147,11 +139,10 @@ struct Table {
     // MSM has run, phi(P) = (beta x, y) of every base at [n, 2n); built on first use
     int fast_ok = 0, phi_ok = 0;
     DevBuf fast;
-    // GLV MSMs over the whole table: packed-29 copies of 2^(c w) P and 2^(c w) phi(P) for every
+    // GLV MSMs over the whole table: radix-2^29 limb copies of 2^(c w) P and 2^(c w) phi(P) for every
     // window w ([w][2n] layout), so all windows share one set of buckets (msm.hip, "shared
     // windows"); built on first use for the window size c in win_c
     int win_ok = 0, win_c = 0, win_W = 0, win_ts = 0, win_m = 1;  // win_m > 1: radix win_m 2^win_c
-    int win_limbs = 1;  // copies in radix-2^29 limbs (1) or packed-29 (0, VKZG_WIN_PACKED probe)
     int win_pair = 0;   // radix copies in the pair layout (SW29::AffP, one 128-B record per signed copy)
     DevBuf win;
     // the first few bases as a table of their own with wider fixed-base windows (lead_table in
@@ -210,8 +201,8 @@ enum WsSlot {
     WS_COUNT_
 };
 
-// a stream and the workspace its launches use: the MSM runs two window slices concurrently
-// (lane 0 = the context's stream + ws, lane 1 = side_stream + ws2)
+// a stream and the workspace its launches use (lane 0 = the context's stream + ws, lane 1 =
+// side_stream + ws2)
 struct Lane {
     hipStream_t st;
     DevBuf* ws;
@@ -248,7 +239,6 @@ struct vc_ctx {
     vk::PinBuf pin_mp;              // the multiproof finish's h - g, copied back ahead of the E commit
     vk::PinBuf pin_ipa;             // the IPA prover's a, x and q terms read by the round kernel (IpaRows)
     vk::PinBuf pin_verkle;          // the verkle extension rows, merged straight into page-locked memory
-    vk::PinBuf pin_verkle2;         // the second buffer of the rows built in pieces (odd pieces)
     vk::PinBuf pin_verkle_lv[2];    // verkle levels' lists (one upload per level; the next level's are
                                     // built into the other one while the current level runs)
     vk::PinBuf pin_norm_vk;         // block products / inverses of the verkle rows' normalisation
@@ -330,6 +320,40 @@ struct vc_ctx {
     } while (0)
 
 namespace vk {
+// what every C ABI entry point holds for its duration: the context's lock and its device as the
+// thread's current one; the per-kernel timers (vc_ctx_enable_timing) are collected on the way out
+struct Guard {
+    vc_ctx* c;
+    std::lock_guard<std::recursive_mutex> lk;
+    explicit Guard(vc_ctx* ctx) : c(ctx), lk(ctx->mu) { (void)hipSetDevice(ctx->device); }
+    ~Guard() {
+        if (c->timing) c->collect_timers();
+    }
+};
+
+// The diagnostics' environment variables, each read here and nowhere else (once per process); they
+// print to stderr and change no result and no launch.
+// VKZG_HOST_TIMING=1: host-side phase times of the MSM, commit and verifier paths
+inline bool host_timing() {
+    static const char* const e = getenv("VKZG_HOST_TIMING");
+    static const bool on = e && atoi(e) != 0;
+    return on;
+}
+// VKZG_VERBOSE: phase laps (some with a stream synchronisation at each lap)
+inline bool verbose() {
+    static const bool on = getenv("VKZG_VERBOSE") != nullptr;
+    return on;
+}
+// VKZG_VERKLE_STAMPS: the host's time at each lap of the device-resident verkle commitment, without
+// synchronising (printed at its end)
+inline bool verkle_stamps() {
+    static const bool on = getenv("VKZG_VERKLE_STAMPS") != nullptr;
+    return on;
+}
+inline double clock_us() {
+    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
 // implemented per translation unit with explicit instantiations
 int device_mad_rate(vc_ctx* ctx, double* tera_per_s);
 int msm_windows(int curve, size_t n, int* c, int* W, int* terms);
@@ -424,13 +448,12 @@ int table_from_acc(vc_ctx* ctx, Table* t, const void* d_acc, size_t n);
 // the results are written there instead of d_out_* and *on_host is set
 // pin_sc: the scalars in ctx->pin_io (host, page-locked) instead of d_scalars (nullptr): uploaded
 // to WS_SCALARS here, or read in place over PCIe by the latency path. overlap: host work run once
-// the commit kernel is enqueued, before the call waits for it. cols: compacted rows (latency path
-// only: VC_E_INVALID otherwise; fb_small_path says whether it runs)
+// the commit kernel is enqueued, before the call waits for it. ipa: the IPA prover's rows made in
+// the kernel (latency path only: VC_E_INVALID otherwise; fb_small_path says whether it runs)
 int msm_batch_run(vc_ctx* ctx, Table* t, size_t width, const void* d_scalars, size_t batch,
                   int mont, void* d_out_xy, uint8_t* d_out_inf, uint64_t* h_out_xy = nullptr,
                   uint8_t* h_out_inf = nullptr, bool* on_host = nullptr, const PinBuf* pin_sc = nullptr,
-                  const std::function<void()>* overlap = nullptr, const StrideCols* cols = nullptr,
-                  const IpaRows* ipa = nullptr);
+                  const std::function<void()>* overlap = nullptr, const IpaRows* ipa = nullptr);
 // whether msm_batch_run of `batch` width-`width` commits takes the latency path
 bool fb_small_path(vc_ctx* ctx, Table* t, size_t width, size_t batch);
 }  // namespace vk

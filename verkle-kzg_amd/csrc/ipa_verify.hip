@@ -168,17 +168,6 @@ __global__ __launch_bounds__(64) void k_ipa_verify_curve(uint32_t* com_xy, const
 }
 
 namespace {
-struct Guard {
-    vc_ctx* c;
-    std::lock_guard<std::recursive_mutex> lk;
-    explicit Guard(vc_ctx* ctx) : c(ctx), lk(ctx->mu) { (void)hipSetDevice(ctx->device); }
-    ~Guard() {
-        if (c->timing) c->collect_timers();
-    }
-};
-double clock_us() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 bool canonical_fr(const uint64_t* w) { return bn::words_below_modulus<BN254Fr>(reinterpret_cast<const uint32_t*>(w)); }
 }  // namespace
 
@@ -222,7 +211,7 @@ extern "C" int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n, co
     if (const char* e = getenv("VKZG_IPA_VERIFY_CHUNK"))
         if (atol(e) > 0) chunk = (size_t)atol(e);
     chunk = std::min(chunk, n);
-    static const bool timing = getenv("VKZG_HOST_TIMING") && atoi(getenv("VKZG_HOST_TIMING")) != 0;
+    const bool timing = host_timing();
 
     DevBuf d_rows(ctx), d_vs(ctx), d_chal(ctx), d_fr(ctx), d_pts(ctx), d_flags(ctx), d_fixed(ctx), d_pw(ctx), d_res(ctx);
     VK_TRY(d_rows.ensure(chunk * (N + 1) * 32));

@@ -89,21 +89,6 @@ __global__ __launch_bounds__(KB_BLOCK) void k_kzg_batch_prep(
 }
 
 namespace {
-struct Guard {
-    vc_ctx* c;
-    std::lock_guard<std::recursive_mutex> lk;
-    explicit Guard(vc_ctx* ctx) : c(ctx), lk(ctx->mu) { (void)hipSetDevice(ctx->device); }
-    ~Guard() {
-        if (c->timing) c->collect_timers();
-    }
-};
-double clock_us() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-bool host_timing() {
-    static const bool on = getenv("VKZG_HOST_TIMING") && atoi(getenv("VKZG_HOST_TIMING")) != 0;
-    return on;
-}
 const uint32_t* w32(const uint64_t* p) { return reinterpret_cast<const uint32_t*>(p); }
 
 struct Batch {

@@ -364,7 +364,7 @@ template <class T>
 __global__ void __launch_bounds__(1024) k_sort_fine(const T* __restrict__ tmp, const uint32_t* __restrict__ base,
                                                    uint32_t nblk, uint32_t bins, uint32_t FB,
                                                    uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted,
-                                                   uint32_t* __restrict__ zero_word, uint32_t cap, uint32_t regs_ok,
+                                                   uint32_t* __restrict__ zero_word, uint32_t cap,
                                                    AccStart* __restrict__ starts, uint32_t M) {
     __shared__ uint32_t h[256], x[256];
     extern __shared__ uint32_t stage[];
@@ -379,7 +379,7 @@ __global__ void __launch_bounds__(1024) k_sort_fine(const T* __restrict__ tmp, c
     // counting pass to the scatter: the bin is read from HBM once, not twice (uniform per block)
     constexpr uint32_t RMAX = 16;
     T er[RMAX];
-    const bool regs = regs_ok != 0 && cap != 0 && end - start <= cap && end - start <= RMAX * blockDim.x;
+    const bool regs = cap != 0 && end - start <= cap && end - start <= RMAX * blockDim.x;
     if (regs) {
 #pragma unroll
         for (uint32_t k = 0; k < RMAX; k++) {
@@ -512,39 +512,13 @@ struct is_affp<FC, BT, std::void_t<typename FC::AffP>> : std::is_same<BT, typena
 template <class C, class BT>
 struct is_fbe : std::is_same<BT, FbE<C>> {};
 
-// straddle merge inside the accumulate (A/B knob VKZG_ACC_MERGE in a -DVKZG_ACC_MERGE_BUILD build;
-// the default build leaves the code out: it grew the kernel to 237 VGPRs and 18,441 instructions).
-// Measured slower: accumulate +0.087 ms, the remaining fix-up 0.083 -> 0.158 ms (profiles/r04/merge_ab/)
-static uint32_t acc_merge() {
-    static const uint32_t v = getenv("VKZG_ACC_MERGE") ? (uint32_t)atoi(getenv("VKZG_ACC_MERGE")) : 0u;
-    return v;
-}
-
-// one lane's value from lane + 1 of the wave (word by word through ds_bpermute)
-template <class T>
-__device__ __forceinline__ T shfl_down1(const T& v) {
-    static_assert(sizeof(T) % 4 == 0, "");
-    constexpr int NW = (int)(sizeof(T) / 4);
-    uint32_t w[NW];
-    __builtin_memcpy(w, &v, sizeof w);
-#pragma unroll
-    for (int k = 0; k < NW; k++) w[k] = (uint32_t)__shfl_down((int)w[k], 1);
-    T r;
-    __builtin_memcpy(&r, w, sizeof w);
-    return r;
-}
-
-// merge: the owner piece of a straddling bucket whose only carry piece is in the next lane of the
-// same wave is added here, after the loop (one general add per lane, all lanes together), and its
-// bucket written: owner_bucket[t] is cleared so the fix-up kernels skip it. Left for the fix-up:
-// lane 63's straddles (the next lane is in another wave) and chains over three or more threads.
 template <class C, class BT = typename C::Aff>
 __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
     const BT* __restrict__ bases, const BT* __restrict__ phi, uint32_t nphi,
     const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets, uint32_t NBtot, uint32_t M,
     typename Fast29<C>::type::Acc* __restrict__ buckets, typename Fast29<C>::type::Acc* __restrict__ carry_in,
     uint8_t* __restrict__ through, typename Fast29<C>::type::Acc* __restrict__ owner_piece,
-    uint32_t* __restrict__ owner_bucket, uint32_t* __restrict__ chain_max, uint32_t merge,
+    uint32_t* __restrict__ owner_bucket, uint32_t* __restrict__ chain_max,
     unsigned long long* __restrict__ clk, const AccStart* __restrict__ starts) {
     using FC = typename Fast29<C>::type;
     using Aff = BT;
@@ -618,7 +592,6 @@ __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
     uint32_t idx = sorted[k];
     uint32_t idx2 = sorted[min(k + 1, e - 1)];
     Pre P = fetch(idx);
-    uint32_t my_through = 0, own_b = NONE;  // for the merge after the loop
     while (true) {
         uint32_t cur = idx;
         typename FC::Aff Q;
@@ -639,14 +612,12 @@ __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
                 buckets[b] = acc;
             } else if (left_open) {
                 carry_in[t] = acc;
-                my_through = right_open ? 2 : 1;
-                through[t] = (uint8_t)my_through;  // 1: carry piece ending here, 2: bucket continues
+                through[t] = right_open ? 2 : 1;  // 1: carry piece ending here, 2: bucket continues
                 // chain end: chain length = carry threads of this bucket
                 if (!right_open && left_open >= 2) atomicMax(chain_max, left_open);
             } else {
                 owner_piece[t] = acc;
                 owner_bucket[t] = b;
-                own_b = b;  // acc keeps the owner piece: it is the thread's last bucket
             }
             if (k == e) break;
             left_open = 0;
@@ -670,22 +641,6 @@ __global__ void __launch_bounds__(256) VK_ACC_OCC k_msm_accumulate(
         clk[2] = __builtin_amdgcn_s_memtime();
         clk[3] = __builtin_amdgcn_s_memrealtime();
     }
-#ifdef VKZG_ACC_MERGE_BUILD
-    if (merge) {  // uniform
-        // the next lane's carry piece (its own store, read back by the thread that wrote it)
-        const typename FC::Acc mine = my_through == 1 ? carry_in[t] : FC::zero();
-        const typename FC::Acc nxt = shfl_down1(mine);
-        const uint32_t nth = (uint32_t)__shfl_down((int)my_through, 1);
-        if (own_b != NONE && (threadIdx.x & 63u) != 63u && nth == 1) {
-            buckets[own_b] = FC::add(acc, nxt);
-            owner_bucket[t] = NONE;
-        }
-    }
-#else
-    (void)merge;
-    (void)my_through;
-    (void)own_b;
-#endif
 }
 
 // radix-29 bucket accumulators -> ec.hpp form, non-empty buckets only (empty ones keep what the
@@ -1152,7 +1107,7 @@ __global__ void __launch_bounds__(256) k_win_next(const typename C::Aff* __restr
 }
 
 // Shared-window copies of a GLV table (Table::win): for w < W, 2^(c w) P_i at [w][i] and
-// 2^(c w) phi(P_i) at [w][n + i], packed-29. A GLV MSM over the whole table then sends every
+// 2^(c w) phi(P_i) at [w][n + i], in radix-2^29 limbs. A GLV MSM over the whole table then sends every
 // window's digits to one set of 2^(c-1) buckets -- the same mixed adds, but one bucket reduction
 // instead of W and no doublings in the host fold. 2 W n points (1.6 GB at n = 2^20, c = 16),
 // built once per table and window size: W - 1 steps of c doublings + a batch normalisation.
@@ -1168,13 +1123,11 @@ static int win_tables(vc_ctx* ctx, Table* t, int c, int W, int ts, uint32_t mul 
     t->win_ok = 0;
     using FA = typename Fast29<C>::type::AffN;  // signed limb form (k_to_limbs_n)
     using FP = typename Fast29<C>::type::AffP;  // pair layout (k_to_limbs_p)
-    // VKZG_WIN_PACKED=1 keeps the packed-29 form (A/B probe: unpacking costs the accumulate ~84 of
-    // 5,044 instructions per add, the limb form 16 B more per gather); the limb form holds
-    // x, y and -y (168 B) so the accumulate never negates
-    static const bool packed = getenv("VKZG_WIN_PACKED") != nullptr;
-    t->win_limbs = packed ? 0 : 1;
-    t->win_pair = (pair && !packed) ? 1 : 0;
-    VK_TRY(t->win.ensure((size_t)W * 2 * n * (packed ? sizeof(Aff) : t->win_pair ? 2 * sizeof(FP) : sizeof(FA))));
+    // radix-2^29 limbs, not the packed-29 form (unpacking cost the accumulate ~84 of 5,044
+    // instructions per add, the limb form 16 B more per gather); the limb form holds x, y and -y
+    // (168 B) so the accumulate never negates
+    t->win_pair = pair ? 1 : 0;
+    VK_TRY(t->win.ensure((size_t)W * 2 * n * (pair ? 2 * sizeof(FP) : sizeof(FA))));
     Table cur;  // 2^(c w) P (affine, Montgomery): normalised by table_from_acc (commit.hip)
     DevBuf nxt, acc;
     VK_TRY(nxt.ensure(n * sizeof(Aff)));
@@ -1191,11 +1144,7 @@ static int win_tables(vc_ctx* ctx, Table* t, int c, int W, int ts, uint32_t mul 
             src = cur.bases.as<Aff>();
         }
         VK_LAUNCH(ctx, "glv_phi", (k_glv_phi<C>), g, 256, 0, src, (uint32_t)n, bls_fq_mont(GLV_BETA), nxt.as<Aff>());
-        if (packed) {
-            Aff* wp = t->win.as<Aff>();
-            VK_LAUNCH(ctx, "to_fast", (k_to_fast<C>), g, 256, 0, src, n, wp + (size_t)w * 2 * n);
-            VK_LAUNCH(ctx, "to_fast", (k_to_fast<C>), g, 256, 0, nxt.as<Aff>(), n, wp + (size_t)w * 2 * n + n);
-        } else if (t->win_pair) {
+        if (pair) {
             FP* wp = t->win.as<FP>();
             VK_LAUNCH(ctx, "to_limbs", (k_to_limbs_p<C>), g, 256, 0, src, n, wp + 2 * ((size_t)w * 2 * n));
             VK_LAUNCH(ctx, "to_limbs", (k_to_limbs_p<C>), g, 256, 0, nxt.as<Aff>(), n, wp + 2 * ((size_t)w * 2 * n + n));
@@ -1257,19 +1206,15 @@ static int sort_entries(vc_ctx* ctx, Lane L, Src src, uint32_t nv, int c, int wb
         if (ctx->timing) ctx->timer_end("msm_scan", ev, st);
     }
     // fine-pass block: 1024 threads once bins average >= 2^15 entries (one block per bin)
-    static const int fine_env = getenv("VKZG_SORT_FINE_BLOCK") ? atoi(getenv("VKZG_SORT_FINE_BLOCK")) : 0;  // probe
     const uint64_t total = (uint64_t)nv * (uint32_t)(we - wb);
-    int fblk = fine_env == 256 || fine_env == 1024 ? fine_env : (total / bins >= (1u << 15) ? 1024 : 256);
+    int fblk = total / bins >= (1u << 15) ? 1024 : 256;
     // LDS staging of the fine scatter (16K entries, 64 KB: two blocks per CU, 1024 threads) when the
     // mean bin leaves it ~40 % headroom (radix 2^20: 11.5K); a bin beyond it scatters directly
-    static const int stage_env = getenv("VKZG_SORT_STAGE") ? atoi(getenv("VKZG_SORT_STAGE")) : 1;  // A/B probe
-    // staged bins of <= 16 entries per thread keep their entries in registers (k_sort_fine);
-    // VKZG_SORT_FINE_REGS=0: A/B probe
-    static const uint32_t fine_regs = !(getenv("VKZG_SORT_FINE_REGS") && atoi(getenv("VKZG_SORT_FINE_REGS")) == 0);
+    // (staged bins of <= 16 entries per thread keep their entries in registers, k_sort_fine)
     uint32_t cap = 0;
-    if (stage_env && total / bins <= 12000) {
+    if (total / bins <= 12000) {
         cap = 16384;
-        if (fine_env == 0) fblk = 1024;
+        fblk = 1024;
     }
     // staged coarse scatter (k_sort_coarse_st): narrow entries, the block's entries in LDS; with
     // several shared bucket sets (windows [s wps, (s + 1) wps) -> set s) one launch per set, so a
@@ -1290,19 +1235,19 @@ static int sort_entries(vc_ctx* ctx, Lane L, Src src, uint32_t nv, int c, int wb
                          NBC, nblk, stride, wps, chunk, counts, base, static_cast<uint32_t*>(tmp), s * bins_l, bins_l);
         }
         VK_LAUNCH_ON(ctx, st, "msm_sort_fine", k_sort_fine<uint32_t>, bins, fblk, cap * 4,
-                     static_cast<const uint32_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs,
+                     static_cast<const uint32_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap,
                      starts, M);
     } else if (narrow) {
         VK_LAUNCH_ON(ctx, st, "msm_sort_coarse", (k_sort_coarse<Src, uint32_t>), nblk, sblk, lds, src, nv, c, wb, we,
                      FB, NBC, nblk, stride, wps, chunk, base, static_cast<uint32_t*>(tmp));
         VK_LAUNCH_ON(ctx, st, "msm_sort_fine", k_sort_fine<uint32_t>, bins, fblk, cap * 4,
-                     static_cast<const uint32_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs,
+                     static_cast<const uint32_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap,
                      starts, M);
     } else {
         VK_LAUNCH_ON(ctx, st, "msm_sort_coarse", (k_sort_coarse<Src, uint64_t>), nblk, sblk, lds, src, nv, c, wb, we,
                      FB, NBC, nblk, stride, wps, chunk, base, static_cast<uint64_t*>(tmp));
         VK_LAUNCH_ON(ctx, st, "msm_sort_fine", k_sort_fine<uint64_t>, bins, fblk, cap * 4,
-                     static_cast<const uint64_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap, fine_regs,
+                     static_cast<const uint64_t*>(tmp), base, nblk, bins, FB, offsets, sorted, zero_word, cap,
                      starts, M);
     }
     return VC_OK;
@@ -1315,11 +1260,7 @@ static int sort_entries(vc_ctx* ctx, Lane L, Src src, uint32_t nv, int c, int wb
 // one fine-sort block and long fix-up chains (measured 0.25 + 0.23 ms at 2^16 with c = 15).
 // the radix shared-window copies in the pair layout (SW29::AffP: one aligned 128-B record per
 // signed copy, 3.76 GB at 2^20 instead of 2.47). Default on: the 2^20 accumulate 2.15 ms against
-// 2.17-2.38 with the (x, y, -y) records (profiles/r04/pair_ab.txt); VKZG_WIN_PAIR=0 for the A/B
-static bool win_pair_on() {
-    static const int env = getenv("VKZG_WIN_PAIR") ? atoi(getenv("VKZG_WIN_PAIR")) : 1;
-    return env != 0;
-}
+// 2.17-2.38 with the (x, y, -y) records (profiles/r04/pair_ab.txt)
 
 static int glv_window(size_t nv) {
     if (nv >= (1u << 19)) return 16;
@@ -1330,11 +1271,6 @@ static int glv_window(size_t nv) {
 // (GlvDigits::ts), so c need not divide 128. Measured at 2^21 terms: c = 19 (7 windows) cuts
 // the accumulate by 0.3-0.45 ms but its 2^18-bucket reduction, the top window's hot buckets in
 // the fix-up and the sort give it all back (3.61 vs 3.60 ms) -- c = 16 stays.
-static int glv_window_shared(size_t nv) {
-    static const int env = getenv("VKZG_MSM_C") ? atoi(getenv("VKZG_MSM_C")) : 0;  // tuning probe
-    if (env >= 8 && env <= 20) return env;
-    return glv_window(nv);
-}
 // bits of the top window of `total` digit bits cut into c-bit windows, as a shortfall: the top
 // window's digits fall into 2^-(shortfall) of its bucket set
 static int top_shortfall(int c, int total) {
@@ -1356,8 +1292,7 @@ static int choose_window(size_t n, int total) {
     else if (n >= (1u << 12)) c0 = 11;
     else if (n >= (1u << 9)) c0 = 9;
     else if (n >= 64) c0 = 7;
-    static const int env = getenv("VKZG_MSM_TOPFIT") ? atoi(getenv("VKZG_MSM_TOPFIT")) : 1;  // A/B probe
-    if (!env || top_shortfall(c0, total) <= 2) return c0;
+    if (top_shortfall(c0, total) <= 2) return c0;
     int best = c0;
     double best_cost = 0.0;
     for (int c = std::max(4, c0 - 5); c <= std::min(16, c0 + 2); c++) {
@@ -1371,9 +1306,9 @@ static int choose_window(size_t n, int total) {
 
 // One window slice [wb, we) of an MSM enqueued on a lane: sort, accumulate, fix-up, reduction and
 // the read-back of its W (J + 1) reduced points; slice_finish waits for it and folds them by
-// Horner over bit positions. msm_run_t can run two slices of a (rank's) window range on the two
-// lanes, staggered: slice 1's sort beside slice 0's accumulate, slice 1's accumulate after slice
-// 0's (an event), beside slice 0's latency-bound fix-up and reduction (off by default, see below).
+// Horner over bit positions. (Two staggered slices of one window range on the two lanes measured
+// no faster at 2^20 BLS12-381, 4.09-4.29 vs 3.98-4.06 ms: a 4-window slice's accumulate fills one
+// wave per SIMD, and the overlapped tail shares the same SIMDs. Removed.)
 template <class C>
 struct MsmSlice {
     using Acc = typename C::Acc;
@@ -1412,7 +1347,7 @@ struct MsmSlice {
     bool direct = false;
     uint32_t epoch = 0, nflags = 0;
     size_t flag_off = 0;
-    double t_launch0 = 0.0;  // VKZG_HOST_TIMING: when the slice's first kernel was launched (us)
+    double t_launch0 = 0.0;  // host_timing(): when the slice's first kernel was launched (us)
     // BLS12-381 radix digits still to be made (msm_run_t leaves the GLV split to slice_enqueue,
     // which fuses the sort histogram into it when the geometry allows): sc == nullptr otherwise
     struct {
@@ -1426,7 +1361,7 @@ struct MsmSlice {
 
 template <class C, class BT, class Src>
 static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const BT* bases, const BT* phi,
-                         uint32_t nphi, hipEvent_t acc_wait, hipEvent_t acc_done) {
+                         uint32_t nphi) {
     using Acc = typename C::Acc;
     using RAcc = FAcc<C>;  // raw radix-29 accumulators of the accumulate / fix-up / reduction
     const Lane L = sl.L;
@@ -1458,18 +1393,15 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
     // one bucket set: the bit sums straight over 2^15 buckets (measured), segments of 4 at 2^18;
     // radix m 2^c: segments of m buckets (S = 2^(c-1) segments)
     if (sl.shared) Lseg = sl.m > 1 ? sl.m : (NB >= (1u << 17) ? 4 : 1);
-    if (const char* el = getenv("VKZG_MSM_LSEG")) Lseg = (uint32_t)std::max(1, atoi(el));  // tuning probe
     const uint32_t S = NB / Lseg;  // power of two
     uint32_t J = 0;
     while ((1u << J) < S) J++;
     // shared windows with segments: the residue form of the reduction (msm_tail.hip k_msm_segr)
-    static const int resid_env = getenv("VKZG_TAIL_RESIDUE") ? atoi(getenv("VKZG_TAIL_RESIDUE")) : 1;  // A/B probe
-    // per-window bucket sets too, up to 8 of them (VKZG_TAIL_RESIDUE=2: shared windows only -- A/B
-    // probe): the segment stage's 2 Lseg dependent adds become Lseg - 1 for Lseg more U sums in the bit
+    // per-window bucket sets too, up to 8 of them: the segment stage's 2 Lseg dependent adds become Lseg - 1 for Lseg more U sums in the bit
     // stage. Measured (`profiles/r03/probes/residue_perwin/`): the GLV variable-base 2^20 MSM (8 sets)
     // tail 0.436 -> 0.38 ms; 16-20 sets (BN254, Bandersnatch) 0.05-0.16 ms slower, so they keep acc_s
     const bool resid_sets = sl.shared || Wr <= 8;
-    const uint32_t nU = (Lseg > 1 && resid_sets && (resid_env == 1 || (resid_env == 2 && sl.shared))) ? Lseg : 1;
+    const uint32_t nU = (Lseg > 1 && resid_sets) ? Lseg : 1;
     const uint32_t Tmax = (uint32_t)((maxL + M - 1) / M);
     hipStream_t st = L.st;
 
@@ -1484,13 +1416,10 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
         FB = lgNB < 7 ? lgNB : 7;
         chunk = 8192;
     }
-    static const int chunk_env = getenv("VKZG_SORT_CHUNK") ? atoi(getenv("VKZG_SORT_CHUNK")) : 0;  // tuning probe
-    static const int fb_env = getenv("VKZG_SORT_FB") ? atoi(getenv("VKZG_SORT_FB")) : 0;           // tuning probe
     // radix buckets: the staged coarse scatter (k_sort_coarse_st) holds a block's chunk x W entries in
     // LDS, so the chunk is the largest power of two that fits 152 KB beside the 2 x bins counters
-    static const int cstage_env = getenv("VKZG_SORT_CSTAGE") ? atoi(getenv("VKZG_SORT_CSTAGE")) : 1;  // A/B probe
     bool cstage = false;
-    if (sl.m > 1 && sl.shared && cstage_env) {
+    if (sl.m > 1 && sl.shared) {
         // one coarse launch per bucket set (sort_entries): a block stages one set's windows
         const uint64_t bins_l = (uint64_t)(NB >> FB);
         const uint32_t Wl = (uint32_t)W / (uint32_t)Wr;
@@ -1504,16 +1433,13 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
     }
     // per-window buckets: one more coarse bit when the fine bins would be too big to stage in LDS
     // (GLV variable-base 2^21 x 8: 16K -> 8K entries; fine pass 0.118 -> 0.041 ms)
-    if (sl.m == 1 && !sl.shared && cstage_env && FB > 1 && load / (NB >> FB) > 12000) FB--;
-    if (chunk_env >= 256) chunk = (uint32_t)chunk_env;
+    if (sl.m == 1 && !sl.shared && FB > 1 && load / (NB >> FB) > 12000) FB--;
     // shared windows: ~64K entries per coarse bin (one 1024-thread k_sort_fine block each) but at
     // least 256 bins (a fine block per CU). Measured at 2^21 x 8 entries (hist + coarse + fine):
     // 0.233 ms at 2^14 entries per bin (256-thread fine blocks), 0.222 at 2^15, 0.204 at 2^16,
     // 0.295 at 2^17 -- bigger bins shorten the scatter's partial-line writes
-    static const int bin_lg = getenv("VKZG_SORT_BIN_LG") ? atoi(getenv("VKZG_SORT_BIN_LG")) : 16;  // tuning probe
-    while (sl.shared && sl.m == 1 && FB > 1 && (load >> bin_lg) > (size_t)(NB >> FB)) FB--;
+    while (sl.shared && sl.m == 1 && FB > 1 && (load >> 16) > (size_t)(NB >> FB)) FB--;
     while (sl.shared && sl.m == 1 && FB > 1 && (NB >> FB) < 256) FB--;
-    if (fb_env >= 1 && fb_env <= (int)std::min<uint32_t>(lgNB, 8)) FB = (uint32_t)fb_env;
     const uint32_t NBC = NB >> FB;
     const uint32_t nblk = (uint32_t)((nv + chunk - 1) / chunk);
     // the staged coarse pass pays for its LDS sort and write-out with >= 4096 entries per block and
@@ -1521,7 +1447,7 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
     // more blocks per CU: GLV variable-base 2^21 x 8, 4-entry runs, 0.129 -> 0.106 ms). Measured
     // slower: BN254 2^20 (16 windows, 98 KB, 0.119 -> 0.169 ms) and the 8-way window slice (1024
     // entries per block, 0.016 -> 0.029 ms)
-    if (sl.m == 1 && cstage_env) {
+    if (sl.m == 1) {
         const uint64_t per_blk = (uint64_t)chunk * (uint32_t)(sl.we - sl.wb), bins_all = (uint64_t)Wr * NBC;
         const uint64_t lds_b = (2 * bins_all + 1 + per_blk) * 4;
         cstage = per_blk >= 4096 && (per_blk >= 10 * bins_all || lds_b <= 64 * 1024);
@@ -1571,18 +1497,14 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
     sl.tail = ws[WS_TAIL].as<Acc>();
 
     bool counts_ready = false;
-    static const bool timing = getenv("VKZG_HOST_TIMING") && atoi(getenv("VKZG_HOST_TIMING")) != 0;
-    if (timing)
-        sl.t_launch0 =
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    if (host_timing()) sl.t_launch0 = clock_us();
     if constexpr (std::is_same<C, BLS381G1>::value) {
         if (!sl.radix.sc.empty()) {
             // whole bucket sets over all their windows, whole sort blocks of scalars: the GLV split
             // of set s writes the sort histogram of its bins [s NBC, (s + 1) NBC) itself
-            static const int fuse_env = getenv("VKZG_RADIX_HIST") ? atoi(getenv("VKZG_RADIX_HIST")) : 1;  // A/B
             const uint32_t rn = sl.radix.n;
             const int ns = (int)sl.radix.sc.size();
-            counts_ready = fuse_env && sl.shared && Wr == ns && sl.wb == 0 && (uint32_t)sl.we == sl.wps * (uint32_t)ns &&
+            counts_ready = sl.shared && Wr == ns && sl.wb == 0 && (uint32_t)sl.we == sl.wps * (uint32_t)ns &&
                            nv == 2 * (size_t)rn && rn % chunk == 0 && (size_t)2 * NBC * 4 <= 64 * 1024;
             for (int s2 = 0; s2 < ns; s2++) {
                 int32_t* dig = sl.radix.dig + (size_t)s2 * sl.wps * nv;
@@ -1605,11 +1527,9 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
                         sl.shared ? (uint32_t)Wr : 1u));
     // entry count L = offsets[NBtot] stays on the device; grids are sized for L <= nv*W;
     // chain_max was cleared by k_sort_fine
-    if (acc_wait) VK_CHECK_HIP(hipStreamWaitEvent(st, acc_wait, 0));
     VK_LAUNCH_ON(ctx, st, "msm_accumulate", (k_msm_accumulate<C, BT>), (Tmax + 255) / 256, 256, 0, bases, phi, nphi,
                  ws[WS_SORTED].as<uint32_t>(), sl.offsets, NBtot, M, sl.buckets, sl.carry, sl.through, sl.owner,
-                 sl.owner_b, sl.chain_max, acc_merge(), (unsigned long long*)ctx->clk_slot(), starts);
-    if (acc_done) VK_CHECK_HIP(hipEventRecord(acc_done, st));
+                 sl.owner_b, sl.chain_max, (unsigned long long*)ctx->clk_slot(), starts);
     // chains up to 2^guard carry pieces are walked serially by their owners; longer ones
     // (adversarial scalars) take the pointer-jumping path in slice_finish
     // (a top window short by f bits loads its buckets 2^f times the mean)
@@ -1617,23 +1537,17 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
     // shared windows: a short top window's digits load 2^-tb of the buckets several times the
     // mean (c = 19: ~310 entries vs 56), so the walk takes chains of up to 16 pieces
     if (sl.shared) sl.guard = std::max<uint32_t>(sl.guard, 4);
-    static const int fix_env = getenv("VKZG_MSM_FIXUP") ? atoi(getenv("VKZG_MSM_FIXUP")) : 0;  // tuning probe
-    if (fix_env == 1)  // guarded pointer-jumping rounds instead of the owner walk
-        VK_TRY(msm_tail_fixup<C>(ctx, L, Tmax, sl.offsets + NBtot, M, sl.buckets, sl.carry, sl.through, sl.owner,
-                                 sl.owner_b, sl.chain_max, sl.guard));
-    else
-        VK_TRY(msm_tail_fixup_walk<C>(ctx, L, sl.offsets, NBtot, M, sl.buckets, sl.carry, sl.owner, 1u << sl.guard,
-                                      sl.owner_b, sl.through, Tmax));
+    VK_TRY(msm_tail_fixup_walk<C>(ctx, L, sl.offsets, NBtot, M, sl.buckets, sl.carry, sl.owner, 1u << sl.guard,
+                                  sl.owner_b, sl.through, Tmax));
     if (sl.skip_reduce) return VC_OK;
     // direct completion: the final stage writes its W (J + nU) points and the chain word straight
     // into the lane's fine-grained page-locked buffer and flags each block; the host polls the flags
     // (slice_finish) -- no read-back copy (a ~4-us blit plus its dispatch) and no stream wake-up
-    // (~10-20 us). VKZG_TAIL_POLL=0 (A/B probe): copy and wait.
-    static const bool poll_env = !(getenv("VKZG_TAIL_POLL") && atoi(getenv("VKZG_TAIL_POLL")) == 0);
+    // (~10-20 us). A lane whose buffer is not fine-grained copies and waits.
     TailDirect td;
     Acc* out = sl.tail;
     sl.direct = false;
-    if (poll_env && L.pin->flags == hipHostMallocCoherent) {
+    if (L.pin->flags == hipHostMallocCoherent) {
         sl.nflags = (uint32_t)Wr * (J + nU);
         sl.flag_off = tail_bytes + 16;
         VK_TRY(L.pin->ensure(sl.flag_off + (size_t)sl.nflags * 4));
@@ -1723,7 +1637,7 @@ static int slice_finish(vc_ctx* ctx, MsmSlice<C>& sl, typename C::Acc* res) {
     memcpy(&sl.Lmax, static_cast<const uint8_t*>(sl.L.pin->p) + sl.tail_bytes, 4);
     if (sl.Lmax > (1u << sl.guard)) {  // rare (heavily repeated scalars): pointer jumping, redo the tail
         VK_TRY(msm_tail_fixup<C>(ctx, sl.L, sl.Tmax, sl.offsets + sl.NBtot, sl.M, sl.buckets, sl.carry, sl.through,
-                                 sl.owner, sl.owner_b, sl.chain_max, 0));
+                                 sl.owner, sl.owner_b, sl.chain_max));
         VK_TRY(msm_tail_reduce<C>(ctx, sl.L, sl.buckets, sl.offsets, sl.NB, sl.Wr, sl.Lseg, sl.S, sl.J, sl.seg,
                                   sl.rs, sl.bsum_part, sl.tail, sl.nU > 1));
         VK_CHECK_HIP(hipMemcpyAsync(sl.ht.data(), sl.tail, sl.ht.size() * sizeof(Acc), hipMemcpyDeviceToHost,
@@ -1775,21 +1689,12 @@ static int slice_finish(vc_ctx* ctx, MsmSlice<C>& sl, typename C::Acc* res) {
     return VC_OK;
 }
 
-// VKZG_HOST_TIMING=1: host-side phases of each MSM on stderr (probe; tools/msm_probe.py)
-static bool host_timing() {
-    static const bool on = getenv("VKZG_HOST_TIMING") && atoi(getenv("VKZG_HOST_TIMING")) != 0;
-    return on;
-}
-static double now_us() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 template <class C, class Fr>
 static int msm_run_t(vc_ctx* ctx, Table* t, size_t offset, const uint32_t* d_sc, size_t n,
                      int mont, int part, int parts, uint32_t* out_acc) {
     using Acc = typename C::Acc;
     using Aff = typename C::Aff;
-    const double t_entry = host_timing() ? now_us() : 0.0;
+    const double t_entry = host_timing() ? clock_us() : 0.0;  // (phases on stderr; tools/msm_probe.py)
     if (n == 0) {
         Acc z = C::zero();
         memcpy(out_acc, &z, sizeof(Acc));
@@ -1807,7 +1712,7 @@ static int msm_run_t(vc_ctx* ctx, Table* t, size_t offset, const uint32_t* d_sc,
     // shared windows (GLV MSM over the whole table): every window into one bucket set through
     // the 2^(c w) copies of the bases (Table::win, built once; up to 8 GB of HBM). The window
     // size then only trades mixed adds (W per term) against one bucket reduction: c = 19 at
-    // 2^21 terms (7 windows instead of 8). VKZG_MSM_SHARED=0 keeps per-window buckets (probe).
+    // 2^21 terms (7 windows instead of 8).
     bool shared = false;
     int top_shift = 0;
     uint32_t radix_m = 1;  // > 1: radix-B shared windows, B = radix_m 2^c
@@ -1819,24 +1724,19 @@ static int msm_run_t(vc_ctx* ctx, Table* t, size_t offset, const uint32_t* d_sc,
         // adds -- into 5 x 2^15 buckets. The power-of-two c = 19 (7 windows) left a 14-bit top
         // window whose digits hit 1 bucket in 16 (chains in the fix-up) and 2^18 buckets to
         // reduce. Window-sliced (multi-GPU) parts keep c = 16: a one-window slice would reduce
-        // the whole bucket set for 1/7 of the adds. VKZG_MSM_RADIX=1: power-of-two windows (probe).
-        static const int radix_env = getenv("VKZG_MSM_RADIX") ? atoi(getenv("VKZG_MSM_RADIX")) : 5;
+        // the whole bucket set for 1/7 of the adds.
         // a point range [offset, offset + n) of >= 2^18 points (one GPU's share of a point-split
         // MSM, vc_msm_device_partial) reads the same whole-table copies, its entries at their table
         // positions (RadixDigits::pt): one copy layout serves whole-table and point-range MSMs
-        static const int range_env = getenv("VKZG_MSM_RANGE") ? atoi(getenv("VKZG_MSM_RANGE")) : 1;  // A/B
         const bool whole = offset == 0 && n == t->n;
         // ranges down to 2^16 points of a >= 2^18-point table: an eighth of 2^20 on the copies (the
         // 163,840-bucket tail is a fixed cost, but a standalone 2^17-term plan took 1.8 ms against
         // ~0.6: profiles/r04/split_probe*.txt)
         const bool big = whole ? nv >= (1u << 19) : (2 * (size_t)t->n >= (1u << 19) && nv >= (1u << 17));
-        if (glv && shared_env && (whole || range_env) && parts == 1 && big && radix_env == 5 &&
-            !getenv("VKZG_MSM_C") && !getenv("VKZG_WIN_PACKED")) {
-            const size_t win_bytes = (size_t)7 * 2 * t->n *
-                                     (win_pair_on() ? 2 * sizeof(typename Fast29<C>::type::AffP)
-                                                    : sizeof(typename Fast29<C>::type::AffN));
+        if (glv && shared_env && parts == 1 && big) {
+            const size_t win_bytes = (size_t)7 * 2 * t->n * 2 * sizeof(typename Fast29<C>::type::AffP);
             if (win_bytes <= (8ull << 30)) {
-                const int st = win_tables<C>(ctx, t, 16, 7, 0, 5, win_pair_on());
+                const int st = win_tables<C>(ctx, t, 16, 7, 0, 5, true);
                 if (st == VC_OK) {
                     shared = true;
                     c = 16;
@@ -1848,7 +1748,7 @@ static int msm_run_t(vc_ctx* ctx, Table* t, size_t offset, const uint32_t* d_sc,
                 }
             }
         }
-        const int cs = glv_window_shared(nv);
+        const int cs = glv_window(nv);
         const int Ws = (GLV_BITS + cs - 1) / cs;
         // top window: GLV_BITS - cs (Ws - 1) bits -> digits up to 2^tb; scaled to fill 2^(cs-1)
         const int tb = GLV_BITS - cs * (Ws - 1);
@@ -1883,48 +1783,30 @@ static int msm_run_t(vc_ctx* ctx, Table* t, size_t offset, const uint32_t* d_sc,
         return VC_OK;
     }
     const uint8_t* inf = t->inf.as<uint8_t>() + offset;
-    // VKZG_MSM_SLICES=2 runs two staggered slices on the two lanes (tuning probe): measured no
-    // faster at 2^20 BLS12-381 (4.09-4.29 vs 3.98-4.06 ms) -- a 4-window slice's accumulate fills
-    // one wave per SIMD (6-13 % below two), and the overlapped tail shares the same SIMDs
-    static const int slices_env = getenv("VKZG_MSM_SLICES") ? atoi(getenv("VKZG_MSM_SLICES")) : 1;
-    const int nsl = (slices_env == 2 && W >= 2 && nv * (size_t)W >= (1u << 22)) ? 2 : 1;
-    MsmSlice<C> sl[2];
-    for (int k = 0; k < nsl; k++) {
-        sl[k].L = ctx->lane(k);
-        sl[k].c = c;
-        sl[k].wb = wb + k * W / nsl;
-        sl[k].we = wb + (k + 1) * W / nsl;
-        sl[k].W = sl[k].we - sl[k].wb;
-        sl[k].shared = shared;
-        sl[k].m = radix_m;
-        sl[k].wps = (uint32_t)Wfull;
-        if (!shared && radix_m == 1 && sl[k].we == Wfull)
-            sl[k].top_f = top_shortfall(c, glv ? GLV_BITS : Fr::BITS + 1);
-    }
-    hipEvent_t fork = nullptr, join = nullptr, acc0 = nullptr;
-    if (nsl == 2) acc0 = ctx->get_event();
+    MsmSlice<C> sl;
+    sl.L = ctx->lane(0);
+    sl.c = c;
+    sl.wb = wb;
+    sl.we = we;
+    sl.W = W;
+    sl.shared = shared;
+    sl.m = radix_m;
+    sl.wps = (uint32_t)Wfull;
+    if (!shared && radix_m == 1 && we == Wfull) sl.top_f = top_shortfall(c, glv ? GLV_BITS : Fr::BITS + 1);
     if (glv) {
         if constexpr (std::is_same<C, BLS381G1>::value) {
             VK_TRY(ctx->ws[WS_GLV_SC].ensure(radix_m > 1 ? nv * 4 * (size_t)Wfull : nv * 16));
             uint4* halves = ctx->ws[WS_GLV_SC].as<uint4>();
             const Aff* dphi = t->fast.as<Aff>() + t->n + offset;
-            if (radix_m > 1 && nsl == 1) {  // the split runs in slice_enqueue (sort histogram fused)
-                sl[0].radix.sc = {d_sc};
-                sl[0].radix.mont = {mont};
-                sl[0].radix.inf = inf;
-                sl[0].radix.n = (uint32_t)n;
-                sl[0].radix.dig = ctx->ws[WS_GLV_SC].as<int32_t>();
-            }
-            else if (radix_m > 1)
-                VK_LAUNCH(ctx, "glv_split", (k_glv_radix<Fr, 5, 16>), (n + 255) / 256, 256, 0, d_sc, inf, (uint32_t)n,
-                          mont, glv_consts(), Wfull, ctx->ws[WS_GLV_SC].as<int32_t>());
-            else
+            if (radix_m > 1) {  // the split runs in slice_enqueue (sort histogram fused)
+                sl.radix.sc = {d_sc};
+                sl.radix.mont = {mont};
+                sl.radix.inf = inf;
+                sl.radix.n = (uint32_t)n;
+                sl.radix.dig = ctx->ws[WS_GLV_SC].as<int32_t>();
+            } else {
                 VK_LAUNCH(ctx, "glv_split", (k_glv_split<Fr>), (n + 255) / 256, 256, 0, d_sc, (uint32_t)n, mont,
                           glv_consts(), halves);
-            if (nsl == 2) {
-                fork = ctx->get_event();
-                VK_CHECK_HIP(hipEventRecord(fork, ctx->stream));
-                VK_CHECK_HIP(hipStreamWaitEvent(ctx->side_stream, fork, 0));
             }
             // [w][2n] limb-form copies: entry w * 2n + i (sort_entries' stride)
             const auto* win = t->win.as<typename Fast29<C>::type::AffN>();
@@ -1933,64 +1815,35 @@ static int msm_run_t(vc_ctx* ctx, Table* t, size_t offset, const uint32_t* d_sc,
                 src.tw = Wfull - 1;
                 src.ts = top_shift;
             }
-            for (int k = 0; k < nsl; k++) {
-                if (radix_m > 1) {
-                    RadixDigits rd{ctx->ws[WS_GLV_SC].as<int32_t>(), (uint32_t)nv};
-                    rd.off = (uint32_t)offset;  // the point range inside the table's copies
-                    rd.half = (uint32_t)n;
-                    rd.gap = (uint32_t)(t->n - n);
-                    sl[k].stride = (uint32_t)(2 * t->n);
-                    if (t->win_pair) {
-                        const auto* wp = t->win.as<typename Fast29<C>::type::AffP>();
-                        VK_TRY(slice_enqueue<C>(ctx, sl[k], rd, nv, wp, wp, 0xffffffffu, k == 1 ? acc0 : nullptr,
-                                                k == 0 ? acc0 : nullptr));
-                    } else {
-                        VK_TRY(slice_enqueue<C>(ctx, sl[k], rd, nv, win, win, 0xffffffffu, k == 1 ? acc0 : nullptr,
-                                                k == 0 ? acc0 : nullptr));
-                    }
-                }
-                else if (shared && !t->win_limbs)  // (power-of-two shared windows: whole tables only)
-                    VK_TRY(slice_enqueue<C>(ctx, sl[k], src, nv, t->win.as<Aff>(), t->win.as<Aff>(), 0xffffffffu,
-                                            k == 1 ? acc0 : nullptr, k == 0 ? acc0 : nullptr));
-                else if (shared)
-                    VK_TRY(slice_enqueue<C>(ctx, sl[k], src, nv, win, win, 0xffffffffu, k == 1 ? acc0 : nullptr,
-                                            k == 0 ? acc0 : nullptr));
-                else
-                    VK_TRY(slice_enqueue<C>(ctx, sl[k], src, nv, bases, dphi, (uint32_t)n, k == 1 ? acc0 : nullptr,
-                                            k == 0 ? acc0 : nullptr));
+            if (radix_m > 1) {  // (the radix copies are in the pair layout)
+                RadixDigits rd{ctx->ws[WS_GLV_SC].as<int32_t>(), (uint32_t)nv};
+                rd.off = (uint32_t)offset;  // the point range inside the table's copies
+                rd.half = (uint32_t)n;
+                rd.gap = (uint32_t)(t->n - n);
+                sl.stride = (uint32_t)(2 * t->n);
+                const auto* wp = t->win.as<typename Fast29<C>::type::AffP>();
+                VK_TRY(slice_enqueue<C>(ctx, sl, rd, nv, wp, wp, 0xffffffffu));
+            } else if (shared) {  // (power-of-two shared windows: whole tables only)
+                VK_TRY(slice_enqueue<C>(ctx, sl, src, nv, win, win, 0xffffffffu));
+            } else {
+                VK_TRY(slice_enqueue<C>(ctx, sl, src, nv, bases, dphi, (uint32_t)n));
             }
         }
     } else {
-        if (nsl == 2) {
-            fork = ctx->get_event();
-            VK_CHECK_HIP(hipEventRecord(fork, ctx->stream));
-            VK_CHECK_HIP(hipStreamWaitEvent(ctx->side_stream, fork, 0));
-        }
-        for (int k = 0; k < nsl; k++)
-            VK_TRY(slice_enqueue<C>(ctx, sl[k], ScalarDigits<Fr>{d_sc, inf, mont}, nv, bases, bases, 0xffffffffu,
-                                    k == 1 ? acc0 : nullptr, k == 0 ? acc0 : nullptr));
+        VK_TRY(slice_enqueue<C>(ctx, sl, ScalarDigits<Fr>{d_sc, inf, mont}, nv, bases, bases, 0xffffffffu));
     }
-    for (int k = 0; k < nsl; k++) VK_TRY(slice_fetch<C>(sl[k]));
-    const double t_enq = host_timing() ? now_us() : 0.0;
-    if (host_timing()) VK_CHECK_HIP(hipStreamSynchronize(sl[nsl - 1].L.st));
-    const double t_sync = host_timing() ? now_us() : 0.0;
-    Acc res = C::zero();
-    for (int k = 0; k < nsl; k++) {
-        Acc r;
-        VK_TRY(slice_finish<C>(ctx, sl[k], &r));
-        res = C::add(res, r);
-    }
+    VK_TRY(slice_fetch<C>(sl));
+    const double t_enq = host_timing() ? clock_us() : 0.0;
+    if (host_timing()) VK_CHECK_HIP(hipStreamSynchronize(sl.L.st));
+    const double t_sync = host_timing() ? clock_us() : 0.0;
+    Acc res;
+    VK_TRY(slice_finish<C>(ctx, sl, &res));
+    // (through the unified Edwards add, which rescales: vc_msm_device_partial hands out these
+    // projective words, and they stay what they were when this summed a list of slices)
+    res = C::add(C::zero(), res);
     if (host_timing())
         fprintf(stderr, "msm_host n=%zu first_launch_us=%.1f enqueue_us=%.1f wait_us=%.1f fold_us=%.1f\n", n,
-                sl[0].t_launch0 - t_entry, t_enq - t_entry, t_sync - t_enq, now_us() - t_sync);
-    if (nsl == 2) {  // later work on the context's stream stays ordered after lane 1
-        join = ctx->get_event();
-        VK_CHECK_HIP(hipEventRecord(join, ctx->side_stream));
-        VK_CHECK_HIP(hipStreamWaitEvent(ctx->stream, join, 0));
-        ctx->event_pool.push_back(fork);  // a wait binds the record it saw: safe to re-record
-        ctx->event_pool.push_back(join);
-        ctx->event_pool.push_back(acc0);
-    }
+                sl.t_launch0 - t_entry, t_enq - t_entry, t_sync - t_enq, clock_us() - t_sync);
     memcpy(out_acc, &res, sizeof(Acc));
     return VC_OK;
 }
@@ -2009,12 +1862,11 @@ static int msm_run_many_t(vc_ctx* ctx, Table* t, const void* const* d_sc, const 
     if constexpr (std::is_same<C, BLS381G1>::value) {
         bool glv = false;
         if (K > 1 && n == t->n && n >= (1u << 18) && n < (1u << 30) && ctx->opt_shared_windows != 0 &&
-            !getenv("VKZG_MSM_RADIX") && !getenv("VKZG_MSM_C") && !getenv("VKZG_WIN_PACKED") &&
             (uint64_t)2 * n * 7 * std::min<size_t>(K, 8) < 0xffffffffull)
             VK_TRY(glv_table_ok(ctx, t, &glv));
         if (glv) {
             VK_TRY(fast_tables<C>(ctx, t, true));
-            const int st = win_tables<C>(ctx, t, 16, 7, 0, 5, win_pair_on());
+            const int st = win_tables<C>(ctx, t, 16, 7, 0, 5, true);
             if (st == VC_E_OOM) t->win.release();
             else if (st != VC_OK) return st;
             batched = st == VC_OK;
@@ -2047,15 +1899,8 @@ static int msm_run_many_t(vc_ctx* ctx, Table* t, const void* const* d_sc, const 
                     sl.radix.sc.push_back(static_cast<const uint32_t*>(d_sc[k]));
                     sl.radix.mont.push_back(mont[k]);
                 }
-                if (t->win_pair) {
-                    const auto* wp = t->win.as<typename Fast29<C>::type::AffP>();
-                    VK_TRY(slice_enqueue<C>(ctx, sl, RadixDigits{sl.radix.dig, (uint32_t)nv}, nv, wp, wp, 0xffffffffu,
-                                            nullptr, nullptr));
-                } else {
-                    const auto* win = t->win.as<typename Fast29<C>::type::AffN>();
-                    VK_TRY(slice_enqueue<C>(ctx, sl, RadixDigits{sl.radix.dig, (uint32_t)nv}, nv, win, win,
-                                            0xffffffffu, nullptr, nullptr));
-                }
+                const auto* wp = t->win.as<typename Fast29<C>::type::AffP>();  // (radix copies: the pair layout)
+                VK_TRY(slice_enqueue<C>(ctx, sl, RadixDigits{sl.radix.dig, (uint32_t)nv}, nv, wp, wp, 0xffffffffu));
                 VK_TRY(slice_fetch<C>(sl));
                 std::vector<Acc> res(Kb);
                 VK_TRY(slice_finish<C>(ctx, sl, res.data()));
@@ -2385,10 +2230,9 @@ static int sparse_commit_dev(vc_ctx* ctx, Table* t, size_t batch, const uint64_t
     using Acc = typename C::Acc;
     if (batch == 0) return VC_OK;
     const size_t nnz = row_ptr[batch];
-    static const bool verbose = getenv("VKZG_VERBOSE") != nullptr;
     auto tic = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
-        if (!verbose) return;
+        if (!verbose()) return;
         (void)hipStreamSynchronize(ctx->stream);
         auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[sparse %zu rows %zu nnz] %s %.3f ms\n", batch, nnz, what,
@@ -2419,7 +2263,6 @@ static int sparse_commit_dev(vc_ctx* ctx, Table* t, size_t batch, const uint64_t
     DevBuf& d_ownb = ctx->ws[WS_OWNER_B];
     DevBuf& d_tmp = ctx->ws[WS_SCAN_TMP];
     uint32_t M = (uint32_t)std::min<size_t>(64, std::max<size_t>(16, maxL / 131072));
-    if (const char* em = getenv("VKZG_SPARSE_M")) M = (uint32_t)std::max(1, atoi(em));  // tuning probe (read per call)
     const uint32_t Tmax = (uint32_t)((maxL + M - 1) / M);
     DevBuf& d_rc = ctx->ws[WS_SP_RC];
     DevBuf& d_chunks = ctx->ws[WS_SP_CHUNKS];
@@ -2506,7 +2349,7 @@ static int sparse_commit_dev(vc_ctx* ctx, Table* t, size_t batch, const uint64_t
         VK_TRY(d_raw.ensure(nch * sizeof(RAcc)));
         VK_LAUNCH(ctx, "sparse_accumulate", (k_msm_accumulate<C, FA>), (Tmax + 255) / 256, 256, 0, tab, tab, 0xffffffffu,
                   d_ent.as<uint32_t>(), d_off.as<uint32_t>(), (uint32_t)nch, M, d_raw.as<RAcc>(), d_carry.as<RAcc>(),
-                  d_thr.as<uint8_t>(), d_own.as<RAcc>(), d_ownb.as<uint32_t>(), chain_max, acc_merge(),
+                  d_thr.as<uint8_t>(), d_own.as<RAcc>(), d_ownb.as<uint32_t>(), chain_max,
                   (unsigned long long*)nullptr, (const AccStart*)nullptr);  // rows are not sorted here: the search
         // straddling chunks merged by the serial walk of their owners, no chain limit: a chunk holds at
         // most CHNZ x W entries, so it spans at most CHNZ W / M + 2 threads. (The pointer-jumping rounds
@@ -2761,7 +2604,7 @@ int msm_windows(int curve, size_t n, int* c, int* W, int* terms) {
     // BLS12-381 tables of subgroup points take the GLV split (2n terms of 127-bit scalars)
     const bool glv = curve == VC_CURVE_BLS12_381 && n >= GLV_MIN_N && n < (1u << 30);
     // (a GLV MSM over a whole table takes the shared-window size, msm_run_t)
-    *c = glv ? glv_window_shared(2 * n) : choose_window(n, bits + 1);
+    *c = glv ? glv_window(2 * n) : choose_window(n, bits + 1);
     *W = glv ? (GLV_BITS + *c - 1) / *c : (bits + 1 + *c - 1) / *c;
     if (terms) *terms = glv ? 2 : 1;
     return VC_OK;
@@ -2826,10 +2669,7 @@ static int msm_run_host_chunks_t(vc_ctx* ctx, Table* t, size_t offset, const uin
         using Acc = typename C::Acc;
         using A = typename Fast29<C>::type;
         using RAcc = FAcc<C>;
-        static const int radix_env = getenv("VKZG_MSM_RADIX") ? atoi(getenv("VKZG_MSM_RADIX")) : 5;
-        static const int range_env = getenv("VKZG_MSM_RANGE") ? atoi(getenv("VKZG_MSM_RANGE")) : 1;
-        if (K < 2 || K > 4 || n >= (1u << 30) || !ctx->opt_shared_windows || radix_env != 5 || !range_env ||
-            getenv("VKZG_MSM_C") || getenv("VKZG_WIN_PACKED") || 2 * (size_t)t->n < (1u << 19))
+        if (K < 2 || K > 4 || n >= (1u << 30) || !ctx->opt_shared_windows || 2 * (size_t)t->n < (1u << 19))
             return VC_OK;
         // chunks of whole 8192-scalar sort blocks, each >= 2^16 points (a point range on the copies)
         const size_t blk = 8192, nb = (n + blk - 1) / blk;
@@ -2839,10 +2679,9 @@ static int msm_run_host_chunks_t(vc_ctx* ctx, Table* t, size_t offset, const uin
         if (!glv) return VC_OK;
         VK_TRY(fast_tables<C>(ctx, t, true));
         {
-            const size_t win_bytes = (size_t)7 * 2 * t->n *
-                                     (win_pair_on() ? 2 * sizeof(typename A::AffP) : sizeof(typename A::AffN));
+            const size_t win_bytes = (size_t)7 * 2 * t->n * 2 * sizeof(typename A::AffP);
             if (win_bytes > (8ull << 30)) return VC_OK;
-            const int st = win_tables<C>(ctx, t, 16, 7, 0, 5, win_pair_on());
+            const int st = win_tables<C>(ctx, t, 16, 7, 0, 5, true);
             if (st == VC_E_OOM) {
                 t->win.release();
                 return VC_OK;
@@ -2908,13 +2747,8 @@ static int msm_run_host_chunks_t(vc_ctx* ctx, Table* t, size_t offset, const uin
             rd.half = (uint32_t)nj;
             rd.gap = (uint32_t)(t->n - nj);
             sl.stride = (uint32_t)(2 * t->n);
-            if (t->win_pair) {
-                const auto* wp = t->win.as<typename A::AffP>();
-                VK_TRY(slice_enqueue<C>(ctx, sl, rd, 2 * nj, wp, wp, 0xffffffffu, nullptr, nullptr));
-            } else {
-                const auto* wn = t->win.as<typename A::AffN>();
-                VK_TRY(slice_enqueue<C>(ctx, sl, rd, 2 * nj, wn, wn, 0xffffffffu, nullptr, nullptr));
-            }
+            const auto* wp = t->win.as<typename A::AffP>();  // (radix copies: the pair layout)
+            VK_TRY(slice_enqueue<C>(ctx, sl, rd, 2 * nj, wp, wp, 0xffffffffu));
             guard[j] = sl.guard;
             VK_LAUNCH(ctx, "msm_merge", (k_bucket_merge<A>), (NB + 255) / 256, 256, 0, bA, bB, sl.offsets, NB,
                       j == 0 ? 1u : 0u);

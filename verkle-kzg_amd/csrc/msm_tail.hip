@@ -72,14 +72,11 @@ __global__ void __launch_bounds__(256) k_fixup_jump(const typename A::Acc* __res
                                                    const uint8_t* __restrict__ through, uint32_t Tmax,
                                                    const uint32_t* __restrict__ Lp, uint32_t M,
                                                    typename A::Acc* __restrict__ val_out,
-                                                   uint32_t* __restrict__ nxt_out, uint32_t span,
-                                                   const uint32_t* __restrict__ chain_max) {
+                                                   uint32_t* __restrict__ nxt_out) {
     uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t T = (*Lp + M - 1) / M;
     if (u >= T || u >= Tmax || through[u] == 0) return;  // no carry piece in thread u
-    // device-guarded round (launched before the host knows the longest chain): a round the
-    // chains do not need passes its input through unchanged
-    const uint32_t n = (chain_max && span >= *chain_max) ? NONE_T : nxt_in[u];
+    const uint32_t n = nxt_in[u];
     if (n == NONE_T) {
         val_out[u] = val_in[u];
         nxt_out[u] = NONE_T;
@@ -580,15 +577,12 @@ __global__ void __launch_bounds__(64 * SUMPART_WAVES) k_msm_sumpart_q(const type
     }
 }
 
-// pointer-jumping rounds r0 <= r < r1 (span 2^r) for a host-known Lmax, or -- guarded -- rounds
-// whose kernels compare span with the device's chain_max: no host sync in the pipeline;
-// msm_tail_fixup_more finishes the rare longer chains afterwards. The carry pieces ping-pong
-// between `carry` and WS_CARRY2 (links: WS_NXT / WS_NXT2), so the parity of r0 says where the
-// latest state is. Buffers hold the raw radix-29 accumulators (FAcc<C>).
+// pointer-jumping rounds r < r1 (span 2^r) for a host-known Lmax. The carry pieces ping-pong
+// between `carry` and WS_CARRY2 (links: WS_NXT / WS_NXT2). Buffers hold the raw radix-29
+// accumulators (FAcc<C>).
 template <class C>
 static int fixup_rounds(vc_ctx* ctx, Lane L, uint32_t T, const uint32_t* Lp, uint32_t M, FAcc<C>* carry,
-                        const uint8_t* through, uint32_t r0, uint32_t r1, const uint32_t* d_chain_max,
-                        const FAcc<C>** sum) {
+                        const uint8_t* through, uint32_t r1, const FAcc<C>** sum) {
     using A = typename Fast29<C>::type;
     using Acc = FAcc<C>;
     VK_TRY(L.ws[WS_CARRY2].ensure((size_t)(T + 8) * sizeof(Acc)));
@@ -598,14 +592,10 @@ static int fixup_rounds(vc_ctx* ctx, Lane L, uint32_t T, const uint32_t* Lp, uin
     Acc* vb = L.ws[WS_CARRY2].as<Acc>();
     uint32_t* na = L.ws[WS_NXT].as<uint32_t>();
     uint32_t* nb = L.ws[WS_NXT2].as<uint32_t>();
-    if (r0 & 1) {  // continuing after an odd number of rounds: the latest state is in the second pair
-        std::swap(va, vb);
-        std::swap(na, nb);
-    }
-    if (r0 == 0) VK_LAUNCH_ON(ctx, L.st, "msm_fixup_init", (k_fixup_init<A>), (T + 255) / 256, 256, 0, through, T, Lp, M, na);
-    for (uint32_t r = r0; r < r1; r++) {
+    VK_LAUNCH_ON(ctx, L.st, "msm_fixup_init", (k_fixup_init<A>), (T + 255) / 256, 256, 0, through, T, Lp, M, na);
+    for (uint32_t r = 0; r < r1; r++) {
         VK_LAUNCH_ON(ctx, L.st, "msm_fixup_jump", (k_fixup_jump<A>), (T + 255) / 256, 256, 0, va, na, through, T, Lp, M, vb,
-                  nb, 1u << r, d_chain_max);
+                     nb);
         std::swap(va, vb);
         std::swap(na, nb);
     }
@@ -616,19 +606,15 @@ static int fixup_rounds(vc_ctx* ctx, Lane L, uint32_t T, const uint32_t* Lp, uin
 template <class C>
 int msm_tail_fixup(vc_ctx* ctx, Lane L, uint32_t T, const uint32_t* Lp, uint32_t M, FAcc<C>* buckets, FAcc<C>* carry,
                    const uint8_t* through, const FAcc<C>* owner, const uint32_t* owner_b,
-                   const uint32_t* d_chain_max, uint32_t guarded) {
+                   const uint32_t* d_chain_max) {
     using A = typename Fast29<C>::type;
     const FAcc<C>* sum = carry;
-    if (guarded) {
-        VK_TRY(fixup_rounds<C>(ctx, L, T, Lp, M, carry, through, 0, guarded, d_chain_max, &sum));
-    } else {
-        uint32_t Lmax = 0;
-        VK_CHECK_HIP(hipMemcpyAsync(&Lmax, d_chain_max, 4, hipMemcpyDeviceToHost, L.st));
-        VK_CHECK_HIP(hipStreamSynchronize(L.st));
-        uint32_t r1 = 0;
-        while (Lmax >= 2 && (1u << r1) < Lmax) r1++;
-        if (r1 > 0) VK_TRY(fixup_rounds<C>(ctx, L, T, Lp, M, carry, through, 0, r1, nullptr, &sum));
-    }
+    uint32_t Lmax = 0;
+    VK_CHECK_HIP(hipMemcpyAsync(&Lmax, d_chain_max, 4, hipMemcpyDeviceToHost, L.st));
+    VK_CHECK_HIP(hipStreamSynchronize(L.st));
+    uint32_t r1 = 0;
+    while (Lmax >= 2 && (1u << r1) < Lmax) r1++;
+    if (r1 > 0) VK_TRY(fixup_rounds<C>(ctx, L, T, Lp, M, carry, through, r1, &sum));
     VK_LAUNCH_ON(ctx, L.st, "msm_fixup", (k_msm_fixup<A>), (T + 255) / 256, 256, 0, buckets, sum, owner, owner_b, T, Lp, M);
     return VC_OK;
 }
@@ -639,13 +625,11 @@ int msm_tail_fixup_walk(vc_ctx* ctx, Lane L, const uint32_t* offsets, uint32_t N
                         const FAcc<C>* carry, const FAcc<C>* owner, uint32_t limit, const uint32_t* owner_b,
                         const uint8_t* through, uint32_t Tmax) {
     using A = typename Fast29<C>::type;
-    static const int quad_env = getenv("VKZG_FIXUP_QUAD") ? atoi(getenv("VKZG_FIXUP_QUAD")) : 1;  // A/B probe
-    static const int own_env = getenv("VKZG_FIXUP_OWN") ? atoi(getenv("VKZG_FIXUP_OWN")) : 1;     // A/B probe
     // fewer accumulate threads than buckets: a lane per owner thread (k_msm_fixup_own). Round 6
     // built a variant with the rare long chains compacted through LDS (one wave per block finishing
     // them) and measured it slower, 0.076 vs 0.072 ms (profiles/r06/tail_trace/; commit 9fc06f9's
     // k_msm_fixup_own_c): removed
-    if (own_env && owner_b && Tmax <= NBtot) {
+    if (owner_b && Tmax <= NBtot) {
         VK_LAUNCH_ON(ctx, L.st, "msm_fixup", (k_msm_fixup_own<A>), (Tmax + 255) / 256, 256, 0, buckets, carry, owner,
                      owner_b, through, Tmax, offsets + NBtot, M, limit);
         return VC_OK;
@@ -654,7 +638,7 @@ int msm_tail_fixup_walk(vc_ctx* ctx, Lane L, const uint32_t* offsets, uint32_t N
     // per-window bucket sets (8 x 2^15) every SIMD already has lane-per-bucket waves and the
     // quads' ~2x instructions per add made the walk slower (0.08 -> 0.115 ms)
     if constexpr (A::quad) {
-        if ((quad_env && NBtot <= 65536) || quad_env == 2) {
+        if (NBtot <= 65536) {
             VK_LAUNCH_ON(ctx, L.st, "msm_fixup", (k_msm_fixup_walk_q<A>), (uint32_t)(((size_t)NBtot * 4 + 255) / 256), 256,
                          0, buckets, carry, owner, offsets, NBtot, M, limit, owner_b);
             return VC_OK;
@@ -662,21 +646,6 @@ int msm_tail_fixup_walk(vc_ctx* ctx, Lane L, const uint32_t* offsets, uint32_t N
     }
     VK_LAUNCH_ON(ctx, L.st, "msm_fixup", (k_msm_fixup_walk<A>), (NBtot + 255) / 256, 256, 0, buckets, carry, owner,
                  offsets, NBtot, M, limit, owner_b);
-    return VC_OK;
-}
-
-// after `guarded` guarded rounds: chains longer than 2^guarded threads (Lmax read back with the
-// results) get their remaining rounds, then the owners are rewritten (idempotent)
-template <class C>
-int msm_tail_fixup_more(vc_ctx* ctx, Lane L, uint32_t T, const uint32_t* Lp, uint32_t M, FAcc<C>* buckets,
-                        FAcc<C>* carry, const uint8_t* through, const FAcc<C>* owner, const uint32_t* owner_b,
-                        uint32_t guarded, uint32_t Lmax) {
-    using A = typename Fast29<C>::type;
-    uint32_t r1 = guarded;
-    while ((1u << r1) < Lmax) r1++;
-    const FAcc<C>* sum = carry;
-    VK_TRY(fixup_rounds<C>(ctx, L, T, Lp, M, carry, through, guarded, r1, nullptr, &sum));
-    VK_LAUNCH_ON(ctx, L.st, "msm_fixup", (k_msm_fixup<A>), (T + 255) / 256, 256, 0, buckets, sum, owner, owner_b, T, Lp, M);
     return VC_OK;
 }
 
@@ -700,10 +669,9 @@ int msm_tail_reduce(vc_ctx* ctx, Lane L, const FAcc<C>* buckets, const uint32_t*
         nU = Lseg;
         usrc = buckets;
         uoff = offsets;
-        static const int segrq_env = getenv("VKZG_SEGR_QUAD") ? atoi(getenv("VKZG_SEGR_QUAD")) : 1;  // A/B probe
         bool quads = false;
         if constexpr (A::quad) {
-            quads = segrq_env != 0 && (size_t)S * W <= 65536;
+            quads = (size_t)S * W <= 65536;
             if (quads)
                 VK_LAUNCH_ON(ctx, L.st, "msm_segsum", (k_msm_segr_q<A>), (S * (uint32_t)W * 4 + 255) / 256, 256, 0,
                              buckets, offsets, NB, W, Lseg, S, Rs);
@@ -712,10 +680,9 @@ int msm_tail_reduce(vc_ctx* ctx, Lane L, const FAcc<C>* buckets, const uint32_t*
             VK_LAUNCH_ON(ctx, L.st, "msm_segsum", (k_msm_segr<A>), (S * (uint32_t)W + 255) / 256, 256, 0, buckets,
                          offsets, NB, W, Lseg, S, Rs);
     } else {
-        static const int segq_env = getenv("VKZG_SEGSUM_QUAD") ? atoi(getenv("VKZG_SEGSUM_QUAD")) : 1;  // A/B probe
         bool quads = false;
         if constexpr (A::quad) {
-            quads = segq_env != 0 && (size_t)S * W <= 65536;
+            quads = (size_t)S * W <= 65536;
             if (quads)
                 VK_LAUNCH_ON(ctx, L.st, "msm_segsum", (k_msm_segsum_q<A>), (S * (uint32_t)W * 4 + 255) / 256, 256, 0,
                              buckets, offsets, NB, W, Lseg, S, accs, Rs);
@@ -757,9 +724,7 @@ extern "C" int vkzg_tail_trace_fetch(unsigned long long* out, size_t words) {
 
 #define VK_INST_TAIL(C)                                                                                      \
     template int msm_tail_fixup<C>(vc_ctx*, Lane, uint32_t, const uint32_t*, uint32_t, FAcc<C>*, FAcc<C>*,           \
-                                   const uint8_t*, const FAcc<C>*, const uint32_t*, const uint32_t*, uint32_t); \
-    template int msm_tail_fixup_more<C>(vc_ctx*, Lane, uint32_t, const uint32_t*, uint32_t, FAcc<C>*, FAcc<C>*,      \
-                                        const uint8_t*, const FAcc<C>*, const uint32_t*, uint32_t, uint32_t);   \
+                                   const uint8_t*, const FAcc<C>*, const uint32_t*, const uint32_t*);          \
     template int msm_tail_fixup_walk<C>(vc_ctx*, Lane, const uint32_t*, uint32_t, uint32_t, FAcc<C>*, const FAcc<C>*, \
                                         const FAcc<C>*, uint32_t, const uint32_t*, const uint8_t*, uint32_t);                                             \
     template int msm_tail_reduce<C>(vc_ctx*, Lane, const FAcc<C>*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, \

@@ -57,8 +57,6 @@ struct TailPlan {
 // per lane: 0.170 -> 0.198 and 0.139 -> 0.179 ms), so several sets keep the bit form.
 inline TailPlan msm_tail_plan(uint32_t S, uint32_t W, uint32_t J, uint32_t nU, bool quad = true,
                               bool u_total = false) {
-    static const int marg_env = getenv("VKZG_TAIL_MARGINAL") ? atoi(getenv("VKZG_TAIL_MARGINAL")) : 1;  // A/B probe
-    static const int urow_env = getenv("VKZG_TAIL_UROW") ? atoi(getenv("VKZG_TAIL_UROW")) : 1;          // A/B probe
     const double bf = quad ? 3.5 : 6.0;
     TailPlan p;
     p.K = msm_bitsum_k(S, W, J, 64, nU);
@@ -66,7 +64,7 @@ inline TailPlan msm_tail_plan(uint32_t S, uint32_t W, uint32_t J, uint32_t nU, b
     p.nb2 = msm_bitsum_pw(S, p.K);
     p.per_w = J * p.nb1 + nU * p.nb2;
     p.slots = p.per_w;
-    if (!(marg_env && J >= 12 && S == (1u << J))) return p;
+    if (!(J >= 12 && S == (1u << J))) return p;
     if ((uint64_t)W * p.per_w > 1024) return p;
     const uint32_t h = J / 2, G = 1u << h, Hn = 1u << (J - h), kl = Hn / 64;  // Hn >= G >= 64
     double best = p.K + bf;
@@ -84,8 +82,7 @@ inline TailPlan msm_tail_plan(uint32_t S, uint32_t W, uint32_t J, uint32_t nU, b
             p.slots = p.per_w;
         }
     }
-    static const int pack_env = getenv("VKZG_TAIL_PACK") ? atoi(getenv("VKZG_TAIL_PACK")) : 1;  // A/B probe
-    if (pack_env && quad && W > 1) {  // several sets: pack 2-4 column / row sums per wave
+    if (quad && W > 1) {  // several sets: pack 2-4 column / row sums per wave
         for (uint32_t k = kl; k <= 32; k++) {
             uint32_t gL = 1, gH = 1;
             while (gL < 16 && Hn * (gL * 2) / 64 <= k) gL *= 2;  // items per lane of a column wave <= k
@@ -108,7 +105,7 @@ inline TailPlan msm_tail_plan(uint32_t S, uint32_t W, uint32_t J, uint32_t nU, b
             }
         }
     }
-    if (urow_env && u_total && nU == 1) {  // U from the row sums (u_total: the U items are the R_s)
+    if (u_total && nU == 1) {  // U from the row sums (u_total: the U items are the R_s)
         for (uint32_t pl = 1; pl <= Hn / G; pl *= 2) {
             if ((uint64_t)W * (G * pl + Hn) > 1024) break;
             const uint32_t k = std::max(Hn / (64 * pl), G / 64);
@@ -129,20 +126,15 @@ inline TailPlan msm_tail_plan(uint32_t S, uint32_t W, uint32_t J, uint32_t nU, b
     }
     return p;
 }
-// guarded = 0: read the longest chain back (host sync) and run exactly the rounds it needs;
-// guarded = r > 0: r device-guarded rounds, no sync (chains up to 2^r threads; longer ones are
-// finished by msm_tail_fixup_more once the caller has read chain_max with its results)
+// the fix-up by pointer jumping: reads the longest chain back (host sync) and runs exactly the
+// rounds it needs
 // raw radix-29 accumulator of curve C (what k_msm_accumulate writes)
 template <class C>
 using FAcc = typename Fast29<C>::type::Acc;
 template <class C>
 int msm_tail_fixup(vc_ctx* ctx, Lane L, uint32_t T, const uint32_t* Lp, uint32_t M, FAcc<C>* buckets, FAcc<C>* carry,
                    const uint8_t* through, const FAcc<C>* owner, const uint32_t* owner_b,
-                   const uint32_t* d_chain_max, uint32_t guarded = 0);
-template <class C>
-int msm_tail_fixup_more(vc_ctx* ctx, Lane L, uint32_t T, const uint32_t* Lp, uint32_t M, FAcc<C>* buckets,
-                        FAcc<C>* carry, const uint8_t* through, const FAcc<C>* owner, const uint32_t* owner_b,
-                        uint32_t guarded, uint32_t Lmax);
+                   const uint32_t* d_chain_max);
 template <class C>
 int msm_tail_fixup_walk(vc_ctx* ctx, Lane L, const uint32_t* offsets, uint32_t NBtot, uint32_t M, FAcc<C>* buckets,
                         const FAcc<C>* carry, const FAcc<C>* owner, uint32_t limit, const uint32_t* owner_b = nullptr,

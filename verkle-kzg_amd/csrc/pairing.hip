@@ -60,15 +60,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 }
 
 namespace {
-struct Guard {
-    vc_ctx* c;
-    std::lock_guard<std::recursive_mutex> lk;
-    explicit Guard(vc_ctx* ctx) : c(ctx), lk(ctx->mu) { (void)hipSetDevice(ctx->device); }
-    ~Guard() {
-        if (c->timing) c->collect_timers();
-    }
-};
-
 // the key's line tables in device memory, uploaded once per (context, key uid)
 int cached_lines(vc_ctx* ctx, const vc_kzg_vk* vk, const LineCoef** out) {
     auto& slot = ctx->dcache["kzg_vk:" + std::to_string(vk->uid)];

@@ -126,21 +126,10 @@ static Fr inner(const Fr* a, const Fr* b, size_t n) {
 
 static bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 
-// VKZG_HOST_TIMING=1: the IPA prover's / verifier's and the multiproof verifier's host and GPU phases on stderr (probe)
-static double verify_clock_us() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-static bool verify_timing() {
-    static const bool on = getenv("VKZG_HOST_TIMING") && atoi(getenv("VKZG_HOST_TIMING")) != 0;
-    return on;
-}
-
 // width-w fixed-base commitments of Montgomery scalars (host) -> canonical affine (host)
 // overlap: host work run while the commit kernel runs (fb_commit_t)
-// cols (optional, latency path only -- fb_small_path): compacted rows (ctx.hpp StrideCols)
 static int commit_batch(vc_ctx* ctx, Table* t, size_t width, const Fr* sc, size_t batch, uint64_t* out_xy,
-                        uint8_t* out_inf, const std::function<void()>* overlap = nullptr,
-                        const StrideCols* cols = nullptr) {
+                        uint8_t* out_inf, const std::function<void()>* overlap = nullptr) {
     const size_t in_bytes = batch * width * 32, out_bytes = batch * 65;
     VK_TRY(ctx->ws[WS_MISC].ensure(out_bytes));
     uint8_t* dxy = ctx->ws[WS_MISC].as<uint8_t>();
@@ -152,7 +141,7 @@ static int commit_batch(vc_ctx* ctx, Table* t, size_t width, const Fr* sc, size_
     memcpy(ctx->pin_io.p, sc, in_bytes);
     bool on_host = false;
     VK_TRY(msm_batch_run(ctx, t, width, nullptr, batch, 1, dxy, dinf, out_xy, out_inf, &on_host, &ctx->pin_io,
-                         overlap, cols));
+                         overlap));
     if (on_host) return VC_OK;
     VK_CHECK_HIP(hipMemcpyAsync(ctx->pin_io.p, dxy, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
@@ -226,11 +215,11 @@ static int msm_points(vc_ctx* ctx, const uint64_t* xy, const uint8_t* inf, const
                       bool filled = false) {
     size_t n = sc.size();
     if (n <= HOST_MSM_MAX) return host_msm(xy, inf, sc.data(), n, out);
-    const double c0 = verify_timing() ? verify_clock_us() : 0.0;
+    const double c0 = host_timing() ? clock_us() : 0.0;
     if (!filled) VK_TRY(bases_fill(ctx, &ctx->scratch, xy, inf, n));
-    if (verify_timing()) {
+    if (host_timing()) {
         VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        fprintf(stderr, "msm_points n=%zu bases_fill_us=%.1f\n", n, verify_clock_us() - c0);
+        fprintf(stderr, "msm_points n=%zu bases_fill_us=%.1f\n", n, clock_us() - c0);
     }
     DevBuf d(ctx);
     VK_TRY(d.ensure(std::max<size_t>(n, 1) * 32));
@@ -281,19 +270,15 @@ int ipa_prove_impl(vc_ctx* ctx, Table* t, size_t N, const std::vector<std::vecto
         s.coeff.assign(N, fe_one<F>());
     });
     // L (R) of a round has non-zeros only at the N / 2 bases i with i mod m >= m / 2 (< m / 2) and
-    // at q. VKZG_IPA_COMPACT=1 (A/B probe) compacts the rows to those N / 2 + 1 bases on the latency
-    // path: half the threads and half the block partials the host adds, but measured slower (prove
-    // 0.80 vs 0.77 ms, kernel 62 vs 56 us per round: profiles/r05/ipa_compact/) -- the zero lanes of
-    // the full rows make the first adds of the block tree identity adds, which the compacted rows
-    // replace by real ones. Off by default.
-    static const bool compact_env = getenv("VKZG_IPA_COMPACT") && atoi(getenv("VKZG_IPA_COMPACT")) == 1;
-    const bool compact = compact_env && fb_small_path(ctx, t, N / 2 + 1, 2 * B);
-    const size_t W = compact ? N / 2 + 1 : N + 1;
+    // at q. (Rows compacted to those N / 2 + 1 bases on the latency path -- half the threads and half
+    // the block partials the host adds -- measured slower, prove 0.80 vs 0.77 ms, kernel 62 vs 56 us
+    // per round: profiles/r05/ipa_compact/. The zero lanes of the full rows make the first adds of
+    // the block tree identity adds, which the compacted rows replace by real ones. Removed.)
+    const size_t W = N + 1;
     // the rows on the device (IpaRows, the latency path's commit kernel): the host keeps a, b and
-    // the q' <a, b> terms; the coefficient rows live in device memory and are folded there.
-    // VKZG_IPA_DEV_ROWS=0 (read once; A/B probe): the host builds every row.
-    static const bool dev_rows_env = !(getenv("VKZG_IPA_DEV_ROWS") && atoi(getenv("VKZG_IPA_DEV_ROWS")) == 0);
-    const bool dev_rows = dev_rows_env && !compact && fb_small_path(ctx, t, N + 1, 2 * B);
+    // the q' <a, b> terms; the coefficient rows live in device memory and are folded there. Off the
+    // latency path the host builds every row.
+    const bool dev_rows = fb_small_path(ctx, t, N + 1, 2 * B);
     DevBuf d_coeff(ctx);
     std::vector<Fr> ones;  // round 0's coefficients (the upload reads it until the first round ends)
     Fr *pa = nullptr, *px = nullptr, *pq = nullptr;
@@ -314,7 +299,7 @@ int ipa_prove_impl(vc_ctx* ctx, Table* t, size_t N, const std::vector<std::vecto
     double lap_fill = 0, lap_commit = 0, lap_fold = 0;
     for (size_t r = 0; r < K; r++) {
         const size_t m = N >> r, half = m / 2;
-        const double c0 = verify_timing() ? verify_clock_us() : 0.0;
+        const double c0 = host_timing() ? clock_us() : 0.0;
         if (dev_rows) {
             par_for([&](size_t p) {
                 IpaState& s = st[p];
@@ -334,18 +319,18 @@ int ipa_prove_impl(vc_ctx* ctx, Table* t, size_t N, const std::vector<std::vecto
             ir.fold = r > 0 ? 1u : 0u;
             ir.m_prev = (uint32_t)(2 * m);
             ir.h_prev = (uint32_t)m;
-            const double c1 = verify_timing() ? verify_clock_us() : 0.0;
+            const double c1 = host_timing() ? clock_us() : 0.0;
             VK_TRY(ctx->ws[WS_MISC].ensure(2 * B * 65));
             uint8_t* dxy = ctx->ws[WS_MISC].as<uint8_t>();
             bool on_host = false;
             VK_TRY(msm_batch_run(ctx, t, N + 1, nullptr, 2 * B, 1, dxy, dxy + 2 * B * 64, oxy.data(), oinf.data(),
-                                 &on_host, nullptr, nullptr, nullptr, &ir));
+                                 &on_host, nullptr, nullptr, &ir));
             if (!on_host) {  // (the latency path returns host results: not expected)
                 VK_CHECK_HIP(hipMemcpyAsync(oxy.data(), dxy, 2 * B * 64, hipMemcpyDeviceToHost, ctx->stream));
                 VK_CHECK_HIP(hipMemcpyAsync(oinf.data(), dxy + 2 * B * 64, 2 * B, hipMemcpyDeviceToHost, ctx->stream));
                 VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
             }
-            const double c2 = verify_timing() ? verify_clock_us() : 0.0;
+            const double c2 = host_timing() ? clock_us() : 0.0;
             par_for([&](size_t p) {
                 IpaState& s = st[p];
                 const uint64_t* Lxy = &oxy[(2 * p) * 8];
@@ -366,55 +351,35 @@ int ipa_prove_impl(vc_ctx* ctx, Table* t, size_t N, const std::vector<std::vecto
                 s.b.resize(half);
                 px[p] = x;  // the next round's kernel folds the coefficients by it
             });
-            if (verify_timing()) {
-                const double c3 = verify_clock_us();
+            if (host_timing()) {
+                const double c3 = clock_us();
                 lap_fill += c1 - c0, lap_commit += c2 - c1, lap_fold += c3 - c2;
             }
             continue;
         }
-        // L (even commits): bases i with i mod m >= half, R (odd): i mod m < half, in index order
-        // -- the k-th is (k / half) m + k mod half (+ half for L) --, then q
-        StrideCols cols;
-        if (compact) {
-            cols.half = (uint32_t)half;
-            cols.m = (uint32_t)m;
-            cols.off_even = (uint32_t)half;
-            cols.off_odd = 0;
-            cols.n_main = (uint32_t)(N / 2);
-            cols.extra = (uint32_t)N;
-        }
+        // L (even commits): bases i with i mod m >= half, R (odd): i mod m < half, then q
         par_for([&](size_t p) {
             IpaState& s = st[p];
             Fr* sL = &sc[(2 * p) * W];
             Fr* sR = &sc[(2 * p + 1) * W];
-            if (compact) {
-                size_t kl = 0, kr = 0;
-                for (size_t i = 0; i < N; i++) {
-                    size_t j = i % m;
-                    if (j >= half) sL[kl++] = fe_mul<F>(s.a[j - half], s.coeff[i]);
-                    else sR[kr++] = fe_mul<F>(s.a[j + half], s.coeff[i]);
-                }
-            } else {
-                // (round 0: every coefficient is one -- the rows are a's halves as they are)
-                for (size_t i = 0; i < N; i++) {
-                    size_t j = i % m;
-                    if (j >= half) {
-                        sL[i] = r == 0 ? s.a[j - half] : fe_mul<F>(s.a[j - half], s.coeff[i]);
-                        sR[i] = fe_zero<F>();
-                    } else {
-                        sR[i] = r == 0 ? s.a[j + half] : fe_mul<F>(s.a[j + half], s.coeff[i]);
-                        sL[i] = fe_zero<F>();
-                    }
+            // (round 0: every coefficient is one -- the rows are a's halves as they are)
+            for (size_t i = 0; i < N; i++) {
+                size_t j = i % m;
+                if (j >= half) {
+                    sL[i] = r == 0 ? s.a[j - half] : fe_mul<F>(s.a[j - half], s.coeff[i]);
+                    sR[i] = fe_zero<F>();
+                } else {
+                    sR[i] = r == 0 ? s.a[j + half] : fe_mul<F>(s.a[j + half], s.coeff[i]);
+                    sL[i] = fe_zero<F>();
                 }
             }
             // q' * <a_L, b_R> = q * (w <a_L, b_R>)
             sL[W - 1] = fe_mul<F>(s.w, inner(&s.a[0], &s.b[half], half));
             sR[W - 1] = fe_mul<F>(s.w, inner(&s.a[half], &s.b[0], half));
         });
-        const double c1 = verify_timing() ? verify_clock_us() : 0.0;
-        VK_TRY(commit_batch(ctx, t, W, sc.data(), 2 * B, oxy.data(), oinf.data(), nullptr,
-                            compact ? &cols : nullptr));
-        const double c2 = verify_timing() ? verify_clock_us() : 0.0;
+        const double c1 = host_timing() ? clock_us() : 0.0;
+        VK_TRY(commit_batch(ctx, t, W, sc.data(), 2 * B, oxy.data(), oinf.data()));
+        const double c2 = host_timing() ? clock_us() : 0.0;
         par_for([&](size_t p) {
             IpaState& s = st[p];
             const uint64_t* Lxy = &oxy[(2 * p) * 8];
@@ -436,12 +401,12 @@ int ipa_prove_impl(vc_ctx* ctx, Table* t, size_t N, const std::vector<std::vecto
             for (size_t i = 0; i < N; i++)
                 if ((i % m) < half) s.coeff[i] = fe_mul<F>(s.coeff[i], x);
         });
-        if (verify_timing()) {
-            const double c3 = verify_clock_us();
+        if (host_timing()) {
+            const double c3 = clock_us();
             lap_fill += c1 - c0, lap_commit += c2 - c1, lap_fold += c3 - c2;
         }
     }
-    if (verify_timing())
+    if (host_timing())
         fprintf(stderr, "[ipa_prove] %zu proofs x %zu rounds: rows %.1f us, L/R commits %.1f us, transcript + folds %.1f us\n",
                 B, K, lap_fill, lap_commit, lap_fold);
     for (size_t p = 0; p < B; p++) {
@@ -459,7 +424,7 @@ int ipa_verify_impl(vc_ctx* ctx, Table* t, size_t N, const Acc& com, const Fr& p
     if (!is_pow2(N) || t->n < N + 1) return VC_E_INVALID;
     size_t K = pr->rounds;
     if ((1ull << K) != N) return VC_E_INVALID;  // gens = g[0..2^rounds], zip with points_coeffs
-    const double t0 = verify_timing() ? verify_clock_us() : 0.0;
+    const double t0 = host_timing() ? clock_us() : 0.0;
     Fr omega = bn254_group_gen(N);
     if (barycentric_panics(N, point)) return VC_E_DOMAIN;
     std::vector<Fr> b = barycentric(N, point, omega);
@@ -525,17 +490,17 @@ int ipa_verify_impl(vc_ctx* ctx, Table* t, size_t N, const Acc& com, const Fr& p
     const bool on_host = vs.size() <= HOST_MSM_MAX;
     const std::function<void()> straus = [&] {
         ran = true;
-        const double s0 = verify_timing() ? verify_clock_us() : 0.0;
+        const double s0 = host_timing() ? clock_us() : 0.0;
         vst = msm_points(ctx, vxy.data(), vinf.data(), vs, &vb);
-        if (verify_timing()) t_straus = verify_clock_us() - s0;
+        if (host_timing()) t_straus = clock_us() - s0;
     };
-    const double t1 = verify_timing() ? verify_clock_us() : 0.0;
+    const double t1 = host_timing() ? clock_us() : 0.0;
     VK_TRY(commit_batch(ctx, t, N + 1, fs.data(), 1, axy, &ainf, on_host ? &straus : nullptr));
     if (!ran) straus();
     VK_TRY(vst);
-    if (verify_timing())
+    if (host_timing())
         fprintf(stderr, "ipa_verify host_prep_us=%.1f commit_and_straus_us=%.1f (straus %.1f)\n", t1 - t0,
-                verify_clock_us() - t1, t_straus);
+                clock_us() - t1, t_straus);
     Acc tot = C::add(acc_of(axy, ainf), vb);
     *result = C::is_zero(tot) ? 1 : 0;
     return VC_OK;
@@ -944,14 +909,6 @@ using namespace vk;
 
 // ---------------------------------------------------------------- C ABI
 namespace {
-struct Guard {
-    vc_ctx* c;
-    std::lock_guard<std::recursive_mutex> lk;
-    explicit Guard(vc_ctx* ctx) : c(ctx), lk(ctx->mu) { (void)hipSetDevice(ctx->device); }
-    ~Guard() {
-        if (c->timing) c->collect_timers();
-    }
-};
 bool proof_ok(const vc_ipa_proof* p) { return p && p->l_xy && p->r_xy && p->l_inf && p->r_inf; }
 }  // namespace
 
@@ -1548,11 +1505,8 @@ __global__ void k_mp_rpow(Fr r, size_t first, size_t n, uint32_t* __restrict__ r
 // result is below (LZ p^2 / R' + p) = (1 + LZ 2^-7) p; the block results are added with one
 // conditional subtraction each, so the running total stays below 2 p over a chunk of CH / LZ
 // blocks, and a last one makes it canonical.
-// Shapes (LZ x CH, A/B knob VKZG_MP_SHAPE): 3 x 16 (round 4's first), 4 x 16, 4 x 32, 6 x 24.
+// Shapes (LZ x CH) measured: 3 x 16 (round 4's first), 4 x 16, 4 x 32, 6 x 24; 4 x 16 is built.
 constexpr uint32_t MP_LZ_MAX = 6;
-struct MpShape {
-    uint32_t lz, ch;
-};
 // one block of <= LZ queries: products into the columns, one Montgomery reduction
 template <uint32_t LZ>
 __device__ __forceinline__ f29<P29> mp_block(const uint4 (&v)[LZ][2], const uint32_t (&qi)[LZ], uint32_t nq,
@@ -1593,7 +1547,7 @@ __device__ __forceinline__ f29<P29> mp_block(const uint4 (&v)[LZ][2], const uint
     return r;
 }
 
-// NT = 1: non-temporal loads (the evaluations are read once per proof; A/B knob VKZG_MP_NT)
+// NT = 1: non-temporal loads (the evaluations are read once per proof)
 template <int NT, uint32_t LZ>
 __device__ __forceinline__ void mp_load(const uint32_t* __restrict__ f, const uint32_t* __restrict__ order, uint32_t u,
                                         uint32_t nq, size_t N, size_t k, uint4 (&v)[LZ][2], uint32_t (&qi)[LZ]) {
@@ -1617,7 +1571,7 @@ __device__ __forceinline__ void mp_load(const uint32_t* __restrict__ f, const ui
 }
 
 // PF = 1: the next block's loads are issued before the current block's arithmetic, so every lane
-// keeps LZ x 32 B in flight while it multiplies (A/B knob VKZG_MP_PF)
+// keeps LZ x 32 B in flight while it multiplies (measured slower; not instantiated)
 template <int NT, uint32_t LZ, uint32_t CH, int PF = 0>
 __global__ void __launch_bounds__(256) k_mp_chunk(const uint32_t* __restrict__ f, const uint32_t* __restrict__ rp,
                                                  const uint32_t* __restrict__ order, const uint32_t* __restrict__ be,
@@ -1681,12 +1635,9 @@ struct MpPlan {
     DevBuf d_rp, d_order, d_be, d_zc, d_part;
     explicit MpPlan(vc_ctx* ctx) : d_rp(ctx), d_order(ctx), d_be(ctx), d_zc(ctx), d_part(ctx) {}
 };
-// block / chunk shape of k_mp_chunk (VKZG_MP_SHAPE: 0 = 3 x 16, 1 = 4 x 16, 2 = 4 x 32, 3 = 6 x 24);
-// 4 x 16 by default: 0.125-0.129 ms against 0.128-0.131 for 3 x 16 (profiles/r04/mp_shape_ab.txt)
-static int mp_shape_index() {
-    static const int shape_env = getenv("VKZG_MP_SHAPE") ? atoi(getenv("VKZG_MP_SHAPE")) : 1;
-    return shape_env >= 0 && shape_env < 4 ? shape_env : 1;
-}
+// block / chunk shape of k_mp_chunk, LZ x CH = 4 x 16: 0.125-0.129 ms against 0.128-0.131 for 3 x 16
+// (profiles/r04/mp_shape_ab.txt)
+constexpr uint32_t MP_LZ = 4, MP_CHUNK = 16;
 static int mp_plan(vc_ctx* ctx, size_t N, size_t Qs, const uint64_t* z, size_t first, const std::vector<uint32_t>& zval,
                    MpPlan* pl) {
     hipStream_t st = ctx->stream;
@@ -1702,8 +1653,6 @@ static int mp_plan(vc_ctx* ctx, size_t N, size_t Qs, const uint64_t* z, size_t f
         if (z[i] >= N || row_of[z[i]] == 0xffffffffu) return VC_E_DOMAIN;
         row[i] = row_of[z[i]];
     }
-    static const MpShape shapes[4] = {{3, 16}, {4, 16}, {4, 32}, {6, 24}};
-    const uint32_t MP_CHUNK = shapes[mp_shape_index()].ch;
     // counting sort of the shard's queries by row, then chunks of <= MP_CHUNK queries
     std::vector<uint32_t> cnt(Z + 1, 0);
     pl->order.resize(Qs);
@@ -1745,17 +1694,9 @@ static int mp_run(vc_ctx* ctx, size_t N, const void* d_data, const Fr& r, MpPlan
     }
     VK_LAUNCH(ctx, "mp_rpow", k_mp_rpow, (Qs + 255) / 256, 256, 0, r, pl.first, Qs, pl.d_rp.as<uint32_t>());
     const uint32_t kblk = (uint32_t)((N + 255) / 256);
-    // non-temporal loads by default: 0.119-0.121 ms (4.43-4.51 TB/s) against 0.125-0.127 at 2^16 x 256
+    // non-temporal loads: 0.119-0.121 ms (4.43-4.51 TB/s) against 0.125-0.127 at 2^16 x 256
     // (profiles/r04/mp_nt_ab.txt)
-    static const int nt_env = getenv("VKZG_MP_NT") ? atoi(getenv("VKZG_MP_NT")) : 1;
-    using KFn = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, size_t, uint32_t, Fr*);
-    static const int pf_env = getenv("VKZG_MP_PF") ? atoi(getenv("VKZG_MP_PF")) : 0;
-    static const KFn kerns[3][4] = {
-        {k_mp_chunk<0, 3, 16>, k_mp_chunk<0, 4, 16>, k_mp_chunk<0, 4, 32>, k_mp_chunk<0, 6, 24>},
-        {k_mp_chunk<1, 3, 16>, k_mp_chunk<1, 4, 16>, k_mp_chunk<1, 4, 32>, k_mp_chunk<1, 6, 24>},
-        {k_mp_chunk<1, 3, 16, 1>, k_mp_chunk<1, 4, 16, 1>, k_mp_chunk<1, 4, 32, 1>, k_mp_chunk<1, 6, 24, 1>}};
-    const KFn kern = kerns[pf_env ? 2 : nt_env ? 1 : 0][mp_shape_index()];
-    VK_LAUNCH(ctx, "mp_chunk", kern, (size_t)pl.nch * kblk, 256, 0, reinterpret_cast<const uint32_t*>(d_data),
+    VK_LAUNCH(ctx, "mp_chunk", (k_mp_chunk<1, MP_LZ, MP_CHUNK>), (size_t)pl.nch * kblk, 256, 0, reinterpret_cast<const uint32_t*>(d_data),
               pl.d_rp.as<uint32_t>(), pl.d_order.as<uint32_t>(), pl.d_be.as<uint32_t>(), N, kblk, pl.d_part.as<Fr>());
     VK_LAUNCH(ctx, "mp_chunk_reduce", k_mp_chunk_reduce, Z * kblk, 256, 0, pl.d_part.as<Fr>(), pl.d_zc.as<uint32_t>(),
               N, kblk, reinterpret_cast<Fr*>(d_S));
@@ -1790,14 +1731,12 @@ static int mp_begin_overlapped(size_t N, size_t Q, const uint64_t* com_xy, const
         }
     };
     // the overlapped transcript fills its records on its own filler thread, not the host pool the
-    // overlapped planning uses: single proof 3.99-4.15 -> 3.84-3.89 ms (`profiles/r04/mp_begin_pool/`;
-    // VKZG_MP_BEGIN_POOL=1 restores the pool, A/B probe)
-    static const bool pool = getenv("VKZG_MP_BEGIN_POOL") && atoi(getenv("VKZG_MP_BEGIN_POOL")) != 0;
+    // overlapped planning uses: single proof 3.99-4.15 -> 3.84-3.89 ms (`profiles/r04/mp_begin_pool/`)
     std::thread th;
     try {
         th = std::thread([&] {
             try {
-                st_b = mp_begin(N, Q, com_xy, com_inf, z, y, tr_out, r_out, pool);
+                st_b = mp_begin(N, Q, com_xy, com_inf, z, y, tr_out, r_out, /*pool_ok=*/false);
             } catch (...) {  // nothing may leave a thread function
                 st_b = VC_E_OOM;
             }
@@ -1869,11 +1808,10 @@ static int mp_finish(vc_ctx* ctx, int scheme, Table* t, size_t N, const std::vec
                      vc_ipa_proof* ipa_proof, uint64_t* kzg_xy, uint8_t* kzg_inf, uint64_t* kzg_y) {
     if (!is_pow2(N) || G < 1 || zval.empty()) return VC_E_INVALID;
     hipStream_t st = ctx->stream;
-    // VKZG_VERBOSE: phase laps on stderr (with a stream sync at each: diagnostics only)
-    static const bool verbose = getenv("VKZG_VERBOSE") != nullptr;
+    // verbose(): phase laps on stderr (with a stream sync at each: diagnostics only)
     auto tic = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
-        if (!verbose) return;
+        if (!verbose()) return;
         (void)hipStreamSynchronize(st);
         const auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[mp_finish] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - tic).count());
@@ -2300,7 +2238,7 @@ static int mp_claim(vc_ctx* ctx, size_t N, size_t Q, const uint64_t* com_xy, con
     if (!is_pow2(N) || N > (size_t(1) << 28)) return VC_E_INVALID;  // tables below are sized by N
     for (size_t i = 0; i < Q; i++)
         if (z[i] >= N) return VC_E_DOMAIN;
-    const double c0 = verify_timing() ? verify_clock_us() : 0.0;
+    const double c0 = host_timing() ? clock_us() : 0.0;
     vc_transcript* tr = nullptr;
     Fr r;
     // the e-coefficient MSM's points (the Q commitments) are uploaded and checked on the GPU while
@@ -2335,15 +2273,15 @@ static int mp_claim(vc_ctx* ctx, size_t N, size_t Q, const uint64_t* com_xy, con
         const unsigned T = host_pool().size();
         host_pool().run([&](unsigned k) { fill(Q * k / T, Q * (k + 1) / T); });
     }
-    const double c1 = verify_timing() ? verify_clock_us() : 0.0;
+    const double c1 = host_timing() ? clock_us() : 0.0;
     Acc e;
     int st = msm_points(ctx, com_xy, com_inf, coef, &e, filled);
     if (st != VC_OK) {
         vc_transcript_free(tr);
         return st;
     }
-    if (verify_timing())
-        fprintf(stderr, "mp_claim Q=%zu transcript+coef_us=%.1f e_msm_us=%.1f\n", Q, c1 - c0, verify_clock_us() - c1);
+    if (host_timing())
+        fprintf(stderr, "mp_claim Q=%zu transcript+coef_us=%.1f e_msm_us=%.1f\n", Q, c1 - c0, clock_us() - c1);
     uint64_t exy[8];
     uint8_t einf;
     aff_of(e, exy, &einf);

@@ -1,6 +1,8 @@
 """Where the time of one 2^k-point MSM goes: wall ms per vc_msm_device (no event timing), then
 the per-kernel averages with event timing on, and the remainder (host Horner, launch gaps,
-the final sync). usage: msm_probe.py [curve] [log_n]"""
+the final sync). usage: msm_probe.py [curve] [log_n]
+VKZG_MSM_SHARED=0 is this tool's own switch (the library does not read it): it sets the context
+option VC_OPT_MSM_SHARED_WINDOWS to 0."""
 import os
 import sys
 import time
