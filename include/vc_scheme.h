@@ -129,6 +129,26 @@ int vc_kzg_prove(vc_ctx* ctx, int table, size_t size, const uint64_t* evals, siz
 /* same with the evaluations already in device memory (canonical, 4 u64 each) */
 int vc_kzg_prove_device(vc_ctx* ctx, int table, size_t size, const void* d_evals, size_t max,
                         const uint64_t* point, uint64_t* proof_xy, uint8_t* proof_inf, uint64_t* y);
+/* n openings in one call: opening i is prove_point of row `row[i]` (row == NULL: row i, and then
+ * rows == n) of `data` (rows x width canonical values, width <= N is the single call's `max`) at
+ * points[i], and gives exactly what vc_kzg_prove(ctx, table, N, data + row[i] * width * 4, width,
+ * points + 4 i, ..) gives. The rows are uploaded and converted once, the openings run in chunks of
+ * at most 16,384: two field launches and one batched fixed-base commit per chunk. BN254 and
+ * BLS12-381, 2 <= N <= 1024.
+ * A status other than VC_OK is decided on the host before any GPU work and leaves the outputs
+ * untouched: VC_E_INVALID (N not a power of two or outside [2, 1024], width > N, a null array with
+ * n > 0, row == NULL with rows != n, a row[i] >= rows, a point >= r), VC_E_RANGE (the table has
+ * fewer than N points), VC_E_DOMAIN for the whole call when a point equals N (Appendix B.4, as the
+ * single call) or is a domain element (z^N == 1) that is not below N (the reference divides by
+ * zero, precompute.rs:86). n == 0 is VC_OK.
+ * proof_xy: n x 2 NL u64; proof_inf: n; y: n x 4 u64. */
+int vc_kzg_prove_many(vc_ctx* ctx, int table, size_t N, size_t rows, size_t width, const uint64_t* data,
+                      const uint32_t* row, const uint64_t* points, size_t n, uint64_t* proof_xy, uint8_t* proof_inf,
+                      uint64_t* y);
+/* same with the rows already in device memory (rows x width canonical values, 4 u64 each) */
+int vc_kzg_prove_many_device(vc_ctx* ctx, int table, size_t N, size_t rows, size_t width, const void* d_data,
+                             const uint32_t* row, const uint64_t* points, size_t n, uint64_t* proof_xy,
+                             uint8_t* proof_inf, uint64_t* y);
 /* commit + prove_point in one call (configs[3]'s unit): C = commit(evals) (kzg/mod.rs:126-134) and
  * the proof at `point` as vc_kzg_prove_device; both MSMs over the SRS run as one batched
  * pipeline (vc_msm_device_many). */

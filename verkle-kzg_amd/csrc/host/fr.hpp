@@ -107,6 +107,27 @@ inline fe<F> fe_from_be_bytes_mod(const uint8_t* b, size_t len) {
     return fe_from_le_bytes_mod<F>(le.data(), len);
 }
 
+// domain generator w_n = gen^((r-1)/n) of any scalar field (the KZG paths: BN254 and BLS12-381)
+template <class Fr_>
+inline fe<Fr_> group_gen_t(uint64_t n, uint32_t gen) {
+    fe<Fr_> e;
+    for (int i = 0; i < Fr_::N; i++) e.v[i] = Fr_::p(i);
+    e.v[0] -= 1;
+    int lg = 0;
+    while ((1ull << lg) < n) lg++;
+    for (int s = 0; s < lg; s++) {
+        for (int i = 0; i < Fr_::N - 1; i++) e.v[i] = (e.v[i] >> 1) | (e.v[i + 1] << 31);
+        e.v[Fr_::N - 1] >>= 1;
+    }
+    return fe_pow_fe<Fr_, Fr_>(mont_from_u64<Fr_>(gen), e);
+}
+template <class Fr_>
+inline uint32_t fr_generator();
+template <>
+inline uint32_t fr_generator<BN254Fr>() { return 5; }
+template <>
+inline uint32_t fr_generator<BLS381Fr>() { return 7; }
+
 // domain generator w_n = 5^((r-1)/n) (GeneralEvaluationDomain radix-2)
 inline Fr bn254_group_gen_uncached(uint64_t n) {
     // (r - 1) / n for power-of-two n <= 2^28: shift r - 1 right by log2 n

@@ -507,26 +507,6 @@ int ipa_verify_impl(vc_ctx* ctx, Table* t, size_t N, const Acc& com, const Fr& p
 }
 
 // ---------------------------------------------------------------- KZG (a3/a4/a5/a6/a7)
-template <class Fr_>
-static fe<Fr_> group_gen_t(uint64_t n, uint32_t gen) {
-    fe<Fr_> e;
-    for (int i = 0; i < Fr_::N; i++) e.v[i] = Fr_::p(i);
-    e.v[0] -= 1;
-    int lg = 0;
-    while ((1ull << lg) < n) lg++;
-    for (int s = 0; s < lg; s++) {
-        for (int i = 0; i < Fr_::N - 1; i++) e.v[i] = (e.v[i] >> 1) | (e.v[i + 1] << 31);
-        e.v[Fr_::N - 1] >>= 1;
-    }
-    return fe_pow_fe<Fr_, Fr_>(mont_from_u64<Fr_>(gen), e);
-}
-template <class Fr_>
-static uint32_t fr_generator();
-template <>
-uint32_t fr_generator<BN254Fr>() { return 5; }
-template <>
-uint32_t fr_generator<BLS381Fr>() { return 7; }
-
 // evals: host (d_evals == false) or device canonical scalars; out_acc != nullptr returns the
 // un-normalised proof accumulator of window slice `part` of `parts` (multi-GPU) instead of
 // the affine proof

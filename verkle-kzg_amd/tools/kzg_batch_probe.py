@@ -10,7 +10,10 @@ Every verdict is checked (the batch accepts; with one y changed it rejects). Tim
 `reps` calls after a warm-up, host-side wall clock around the whole call. The split comes from a
 child process run with VKZG_HOST_TIMING=1 (the library prints the phases, synchronising between
 them, so their sum exceeds the untimed call).
-usage: kzg_batch_probe.py [--out DIR] [--reps N] [--sizes a,b,c]
+With --real the openings are a prover's: n random rows of a 256-point key, committed by
+vc_msm_batch and opened by vc_kzg_prove_many, every other point in the domain (the rows and points
+of tools/kzg_prove_many_probe.py); the result goes to DIR/probe_real.json.
+usage: kzg_batch_probe.py [--out DIR] [--reps N] [--sizes a,b,c] [--real]
 Writes DIR/probe.json (default: profiles/r10/kzg_verify_batch under the repository root)."""
 import argparse
 import ctypes
@@ -43,6 +46,18 @@ def openings(e, n):
     return xy, inf, pts, xy.copy(), inf.copy(), ys
 
 
+def real_openings(e, n):
+    import kzg_prove_many_probe as pm
+    kz = getattr(e, "_probe_kzg", None)
+    if kz is None:
+        kz = e._probe_kzg = scheme.KZG(e, pm.N, secret=SECRET)
+    data, pts = pm.openings(n, 12 + n)
+    cxy, cinf = e.msm_batch(kz.table, data, pm.N)
+    out = (np.zeros((n, 8), dtype=np.uint64), np.zeros(n, dtype=np.uint8), np.zeros((n, 4), dtype=np.uint64))
+    pm.many(lib(), e, kz.table, n, data, pts, out)
+    return (np.ascontiguousarray(cxy, dtype=np.uint64), np.ascontiguousarray(cinf, dtype=np.uint8), pts) + out
+
+
 def batch_call(L, e, vk, n, a, seed):
     P = scheme._p
     res = ctypes.c_int()
@@ -51,14 +66,14 @@ def batch_call(L, e, vk, n, a, seed):
     return res.value
 
 
-def split(sizes, reps):
+def split(sizes, reps, real):
     """child: the timed phases of `reps` calls per size on stderr (VKZG_HOST_TIMING=1)"""
     L = lib()
     e = vkzg.Engine("bn254", 0)
-    vk = scheme.KZGVerifyingKey(scheme.kzg_g2_from_secret(SECRET), SIZE)
+    vk = scheme.KZGVerifyingKey(scheme.kzg_g2_from_secret(SECRET), 256 if real else SIZE)
     seed = np.frombuffer(bytes(range(32)), dtype=np.uint8).copy()
     for n in sizes:
-        a = openings(e, n)
+        a = (real_openings if real else openings)(e, n)
         for _ in range(reps + 1):
             assert batch_call(L, e, vk, n, a, seed) == 1
     e.close()
@@ -70,16 +85,17 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="256,4096,65536")
     ap.add_argument("--split-child", action="store_true")
+    ap.add_argument("--real", action="store_true")
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(",")]
     if a.split_child:
-        split(sizes, a.reps)
+        split(sizes, a.reps, a.real)
         return
-    res = {"reps": a.reps, "batch": {}, "many": {}, "split_us": {}}
+    res = {"reps": a.reps, "real_openings": a.real, "batch": {}, "many": {}, "split_us": {}}
     # the split first, in a process of its own (the timing switch is read once per process)
     env = dict(os.environ, VKZG_HOST_TIMING="1")
     child = subprocess.run([sys.executable, os.path.abspath(__file__), "--split-child", "--reps", str(a.reps),
-                            "--sizes", a.sizes], env=env, stderr=subprocess.PIPE, text=True, timeout=900)
+                            "--sizes", a.sizes] + (["--real"] if a.real else []), env=env, stderr=subprocess.PIPE, text=True, timeout=900)
     if child.returncode != 0:
         sys.stderr.write(child.stderr[-4000:])
         raise SystemExit(f"split child failed with status {child.returncode}")
@@ -96,10 +112,10 @@ def main():
     L = lib()
     P = scheme._p
     e = vkzg.Engine("bn254", 0)
-    vk = scheme.KZGVerifyingKey(scheme.kzg_g2_from_secret(SECRET), SIZE)
+    vk = scheme.KZGVerifyingKey(scheme.kzg_g2_from_secret(SECRET), 256 if a.real else SIZE)
     seed = np.frombuffer(bytes(range(32)), dtype=np.uint8).copy()
     for n in sizes:
-        arr = openings(e, n)
+        arr = (real_openings if a.real else openings)(e, n)
         tb, tm = [], []
         out = np.zeros(n, dtype=np.uint8)
         for rep in range(a.reps + 1):
@@ -114,7 +130,7 @@ def main():
                 tb.append(t1 - t0)
                 tm.append(t2 - t1)
         bad = [x.copy() for x in arr]
-        bad[5][n // 2, 0] = 1                           # one y changed: the batch is rejected
+        bad[5][n // 2, 0] ^= 1                          # one y changed: the batch is rejected
         assert batch_call(L, e, vk, n, bad, seed) == 0
         b, m = float(np.median(tb)), float(np.median(tm))
         res["batch"][str(n)] = {"seconds": b, "openings_per_s": n / b}
@@ -122,7 +138,7 @@ def main():
         print(f"n = {n:6d}: verify_batch {b * 1e3:.3f} ms, verify_many {m * 1e3:.2f} ms ({m / b:.1f} x)", flush=True)
     e.close()
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "probe.json"), "w") as f:
+    with open(os.path.join(a.out, "probe_real.json" if a.real else "probe.json"), "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res))

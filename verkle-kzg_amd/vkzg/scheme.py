@@ -517,6 +517,31 @@ class KZG:
     def prove(self, commitment, index, data):
         return self.prove_point(commitment, index, data)
 
+    def prove_batch_points(self, commitments, points, datas, rows=None):
+        """n openings in one call (vc_kzg_prove_many): opening i is prove_point of datas[rows[i]]
+        (rows None: datas[i], one data per point) at points[i] -> list of {"proof", "y"}. The datas
+        have one length; the commitments are unused, as in prove_point. VCError(VC_E_DOMAIN) for the
+        whole call when one point makes prove_point fail."""
+        n = len(points)
+        if n == 0:
+            return []
+        width = len(datas[0].evals)
+        if any(len(d.evals) != width for d in datas):
+            raise ValueError("one batch proves data of one length")
+        ev = datas[0].limbs() if len(datas) == 1 else np.concatenate([d.limbs() for d in datas])
+        ev = np.ascontiguousarray(ev)
+        pts = ints_to_limbs([int(p) % R_BN254 for p in points], 4)
+        row = np.ascontiguousarray(np.asarray(rows, dtype=np.uint32)) if rows is not None else None
+        if row is not None and row.shape != (n,):
+            raise ValueError("rows: one data index per point")
+        pxy = np.zeros((n, 8), dtype=np.uint64)
+        pinf = np.zeros(n, dtype=np.uint8)
+        ys = np.zeros((n, 4), dtype=np.uint64)
+        check(lib().vc_kzg_prove_many(self.engine.h, self.table, self.size, len(datas), width, _p(ev),
+                                      _p(row) if row is not None else None, _p(pts), n, _p(pxy), _p(pinf), _p(ys)),
+              "kzg_prove_many")
+        return [{"proof": _pt(pxy[i], pinf[i]), "y": limbs_to_int(ys[i])} for i in range(n)]
+
     def prove_all_points(self, data, mode=0):
         """KZG::prove_all_points (kzg/mod.rs:200-235) -- mode 0: the reference's computation
         exactly (its h_hat values, y = data[i]); mode 1: the FK opening proofs at every domain
