@@ -10,8 +10,8 @@
  * VC_OK or a VC_E_* status (vc_msm.h).  The reference leaves its batch methods `todo!()`
  * (prove_batch / verify_batch, ipa/mod.rs:156-189, kzg/mod.rs:156-197); here vc_ipa_prove takes a
  * batch, and vc_ipa_verify_many / vc_kzg_verify_many verify n independent openings with one verdict
- * each (what verify_batch would return per entry); vc_kzg_verify_batch is the aggregated
- * single-verdict check for KZG (IPA has none).
+ * each (what verify_batch would return per entry); vc_kzg_verify_batch and vc_ipa_verify_batch are
+ * the aggregated single-verdict checks.
  *
  * Scope: the protocol layer is instantiated for BN254 (the only curve the reference runs,
  * vector-commit/Cargo.toml:15).  The MSM / commit engines (vc_msm.h) also serve BLS12-381 G1
@@ -109,6 +109,46 @@ int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n,
                        const uint64_t* com_xy, const uint8_t* com_inf, const uint64_t* points,
                        const uint64_t* l_xy, const uint8_t* l_inf, const uint64_t* r_xy, const uint8_t* r_inf,
                        const uint64_t* tip, const uint64_t* y, vc_transcript** transcripts, uint8_t* results);
+/* One combined check for n openings ("are all of these valid?"; the reference names it
+ * verify_batch, ipa/mod.rs:183-189, and leaves it todo!()). Let E_j be the left side of the identity
+ * low_level_verify_ipa checks for entry j (the identity exactly when the entry is valid), sigma_j = 1
+ * for a point below N and z_j^N - 1 otherwise (non-zero: domain elements not below N are refused).
+ * With one challenge rho:
+ *   S = sum_j rho^j sigma_j E_j,   accept  <=>  S is the identity.
+ * A batch of valid entries is accepted for every rho; a batch with an invalid entry is accepted for
+ * at most n - 1 of the r values of rho. rho = vc_hash_to_field(seed, 32, dst = "vkzg-ipa-batch"): the
+ * verifier draws the seed itself once it holds the inputs; a given seed makes the call
+ * deterministic. Layouts and status rules are vc_ipa_verify_many's, with one more bound: N <= 256
+ * (the fold keeps a lane's columns of the fixed row in registers), VC_E_INVALID above it. */
+/* rho for a seed (host, no context) */
+int vc_ipa_batch_challenge(const uint8_t seed[32], uint64_t* rho_fr);
+/* [w, x_0 .. x_{K-1}] of every entry's fresh "ipa" transcript, canonical: out n x (1 + K) x 4.
+ * ctx == NULL: host pool; ctx != NULL: the device kernel (a lane per entry). No N <= 256 bound. */
+int vc_ipa_challenges_many(vc_ctx* ctx, size_t N, size_t n, const uint64_t* com_xy, const uint8_t* com_inf,
+                           const uint64_t* points, const uint64_t* y, const uint64_t* l_xy, const uint8_t* l_inf,
+                           const uint64_t* r_xy, const uint8_t* r_inf, uint64_t* out);
+/* the fold alone: S as a canonical affine point. *malformed = 1 (S unspecified) when any entry is
+ * malformed in vc_ipa_verify_many's sense. ctx != NULL: device path over the table's CRS (crs_xy
+ * ignored). ctx == NULL: host path (host pool) over crs_xy, the N + 1 points g_0 .. g_{N-1}, q as
+ * canonical affine x[4] y[4] -- the check of the fold against the oracle on a machine without a
+ * GPU, not a product path. VC_E_INVALID also for rho_fr >= r. */
+int vc_ipa_batch_fold(vc_ctx* ctx, int table, const uint64_t* crs_xy, size_t N, size_t n, const uint64_t* com_xy,
+                      const uint8_t* com_inf, const uint64_t* points, const uint64_t* l_xy, const uint8_t* l_inf,
+                      const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* tip, const uint64_t* y,
+                      vc_transcript** transcripts, const uint64_t* rho_fr, uint64_t* s_xy, uint8_t* s_inf,
+                      int* malformed);
+/* *result = 1 when the combined check accepts, else 0. seed32 == NULL: 32 bytes of OS entropy
+ * (getrandom). results: NULL, or n bytes: all 1 when the check accepts; when it rejects (a malformed
+ * entry included) vc_ipa_verify_many's verdicts, so a rejecting call costs the fold plus that call.
+ * transcripts: NULL (every transcript a fresh "ipa" one, hashed on the device), or n handles as
+ * vc_ipa_verify_many takes them (then all transcripts run on the host pool and the handles advance as
+ * there, once). VC_E_DOMAIN before any GPU work with nothing written; a malformed proof entry gives
+ * *result = 0 with VC_OK; n = 0: VC_OK, *result = 1. Chunks of at most 65536 proofs: the device
+ * workspace does not grow with n. */
+int vc_ipa_verify_batch(vc_ctx* ctx, int table, size_t N, size_t n, const uint64_t* com_xy, const uint8_t* com_inf,
+                        const uint64_t* points, const uint64_t* l_xy, const uint8_t* l_inf, const uint64_t* r_xy,
+                        const uint8_t* r_inf, const uint64_t* tip, const uint64_t* y, vc_transcript** transcripts,
+                        const uint8_t* seed32, int* result, uint8_t* results);
 /* prove_commitment (:199-234): proof of knowledge of the first n = data.max() + 1 values
  * behind a commitment (L, R per round, tip; y is set to 0). n must be a power of two: the
  * reference's assert in vec_add_and_distribute (utils.rs:37) panics on any odd split above 1

@@ -171,6 +171,30 @@ namespace {
 bool canonical_fr(const uint64_t* w) { return bn::words_below_modulus<BN254Fr>(reinterpret_cast<const uint32_t*>(w)); }
 }  // namespace
 
+// (shared with vc_ipa_verify_batch's prior-transcript path, ipa_batch.hip)
+void ipa_host_challenges(size_t lo, size_t cnt, int K, const uint64_t* com_xy, const uint8_t* com_inf,
+                         const uint64_t* points, const uint64_t* y, const uint64_t* l_xy, const uint8_t* l_inf,
+                         const uint64_t* r_xy, const uint8_t* r_inf, vc_transcript** transcripts, Fr* chal) {
+    using F = BN254Fr;
+    pool_for(0, cnt, 16, [&](size_t j) {
+        const size_t p = lo + j;
+        const bool own = !(transcripts && transcripts[p]);
+        vc_transcript* tr = own ? vc_transcript_new("ipa") : transcripts[p];
+        transcript_append_point(tr, com_xy + 8 * p, com_inf[p] != 0, "C");
+        transcript_append_fr(tr, canon_to_mont<F>(points + 4 * p), "input point");
+        transcript_append_fr(tr, canon_to_mont<F>(y + 4 * p), "output point");
+        Fr* c = &chal[j * (size_t)(K + 1)];
+        c[0] = transcript_digest(tr, "w");
+        for (int k = 0; k < K; k++) {
+            const size_t at = p * (size_t)K + (size_t)k;
+            transcript_append_point(tr, l_xy + 8 * at, l_inf[at] != 0, "L");
+            transcript_append_point(tr, r_xy + 8 * at, r_inf[at] != 0, "R");
+            c[1 + k] = transcript_digest(tr, "x");
+        }
+        if (own) vc_transcript_free(tr);
+    });
+}
+
 }  // namespace vk
 
 using namespace vk;
@@ -254,23 +278,7 @@ extern "C" int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n, co
     auto run_transcripts = [&](size_t lo, size_t cnt, std::vector<Fr>& chal) {
         const double c0 = timing ? clock_us() : 0.0;
         chal.resize(cnt * (size_t)(K + 1));
-        pool_for(0, cnt, 16, [&](size_t j) {
-            const size_t p = lo + j;
-            const bool own = !(transcripts && transcripts[p]);
-            vc_transcript* tr = own ? vc_transcript_new("ipa") : transcripts[p];
-            transcript_append_point(tr, com_xy + 8 * p, com_inf[p] != 0, "C");
-            transcript_append_fr(tr, canon_to_mont<F>(points + 4 * p), "input point");
-            transcript_append_fr(tr, canon_to_mont<F>(y + 4 * p), "output point");
-            Fr* c = &chal[j * (size_t)(K + 1)];
-            c[0] = transcript_digest(tr, "w");
-            for (int k = 0; k < K; k++) {
-                const size_t at = p * (size_t)K + (size_t)k;
-                transcript_append_point(tr, l_xy + 8 * at, l_inf[at] != 0, "L");
-                transcript_append_point(tr, r_xy + 8 * at, r_inf[at] != 0, "R");
-                c[1 + k] = transcript_digest(tr, "x");
-            }
-            if (own) vc_transcript_free(tr);
-        });
+        ipa_host_challenges(lo, cnt, K, com_xy, com_inf, points, y, l_xy, l_inf, r_xy, r_inf, transcripts, chal.data());
         if (timing) lap_tr += clock_us() - c0;
     };
     std::vector<Fr> chal[2];

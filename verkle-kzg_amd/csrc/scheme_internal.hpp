@@ -23,6 +23,12 @@ using RecordFill = std::function<void(size_t lo, size_t hi, uint8_t* out)>;
 Fr transcript_digest_records(vc_transcript* t, size_t nrec, size_t rec, const RecordFill& fill, const char* label,
                              bool pool_ok);
 Fr to_data_item_host(const uint64_t* xy, bool inf);
+// [w, x_0 .. x_{K-1}] (Montgomery) of entries [lo, lo + cnt) of vc_ipa_verify_many's arrays into
+// chal[0 .. cnt (K + 1)), on the host pool; transcripts: NULL, or handles indexed by entry (NULL:
+// fresh "ipa"), advanced as vc_ipa_verify advances them (ipa_verify.hip)
+void ipa_host_challenges(size_t lo, size_t cnt, int K, const uint64_t* com_xy, const uint8_t* com_inf,
+                         const uint64_t* points, const uint64_t* y, const uint64_t* l_xy, const uint8_t* l_inf,
+                         const uint64_t* r_xy, const uint8_t* r_inf, vc_transcript** transcripts, Fr* chal);
 // vc_multiproof_begin + vc_multiproof_accumulate of the query shard [first, first + Qs), the host
 // transcript on a helper thread while this thread plans the shard (scheme.hip); r_out canonical
 // the number of distinct z (rows of the per-point sums); VC_E_DOMAIN for z >= N

@@ -315,6 +315,69 @@ class IPA:
                                        ctypes.cast(trs, _P) if trs is not None else None, _p(out)), "ipa_verify_many")
         return [bool(v) and g for v, g in zip(out, good)]
 
+    @staticmethod
+    def _handles(transcripts, n):
+        if transcripts is None or not any(t is not None for t in transcripts):
+            return None
+        return ctypes.cast((_P * n)(*[(t.h if t is not None else None) for t in transcripts]), _P)
+
+    def challenges_many(self, commitments, points, proofs, device=True):
+        """[w, x_0 .. x_{K-1}] of every opening's fresh "ipa" transcript (vc_ipa_challenges_many) ->
+        list of (w, [x_k]); device=False: the host pool instead of the device kernel."""
+        n = len(proofs)
+        if n == 0:
+            return []
+        (cxy, cinf, pts, lxy, linf, rxy, rinf, _, ys), good = self._verify_many_arrays(commitments, points, proofs)
+        if not all(good):
+            raise ValueError("every proof needs log2 N rounds")
+        K = _log2(self.N)
+        out = np.zeros((n, 1 + K, 4), dtype=np.uint64)
+        check(lib().vc_ipa_challenges_many(self.engine.h if device else None, self.N, n, _p(cxy), _p(cinf), _p(pts),
+                                           _p(ys), _p(lxy), _p(linf), _p(rxy), _p(rinf), _p(out)), "ipa_challenges_many")
+        return [(limbs_to_int(out[i, 0]), [limbs_to_int(out[i, 1 + k]) for k in range(K)]) for i in range(n)]
+
+    def batch_fold(self, commitments, points, proofs, rho, transcripts=None, device=True):
+        """The fold of vc_ipa_verify_batch alone (vc_ipa_batch_fold): the point S for the challenge
+        rho (None: the identity), or False when an entry is malformed. device=False: the host path
+        over this CRS (the oracle check without a GPU, not a product path)."""
+        n = len(proofs)
+        arrs, good = self._verify_many_arrays(commitments, points, proofs) if n else ((None,) * 9, [])
+        if not all(good):
+            return False
+        ptr = [_p(a) if a is not None else None for a in arrs]
+        crs, _ = _pt_arrays(list(self.g) + [self.q])
+        out = np.zeros(8, dtype=np.uint64)
+        inf = np.zeros(1, dtype=np.uint8)
+        bad = ctypes.c_int()
+        check(lib().vc_ipa_batch_fold(self.engine.h if device else None, self.table, _p(crs), self.N, n, *ptr,
+                                      self._handles(transcripts, n), _p(_fr_raw(rho)), _p(out), _p(inf),
+                                      ctypes.byref(bad)), "ipa_batch_fold")
+        if bad.value:
+            return False
+        return _pt(out, inf[0])
+
+    def verify_batch(self, commitments, points, proofs, seed=None, locate=False, transcripts=None):
+        """One combined check for n openings (vc_ipa_verify_batch) -> bool: are all of them valid?
+        seed: 32 bytes the verifier draws after it holds the inputs (None: OS entropy). locate=True ->
+        (bool, list of bool): when the combined check rejects, the per-opening verdicts of verify_many
+        say which ones are bad. transcripts: as verify_many's (prior states, advanced once)."""
+        n = len(proofs)
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        arrs, good = self._verify_many_arrays(commitments, points, proofs) if n else ((None,) * 9, [])
+        ptr = [_p(a) if a is not None else None for a in arrs]
+        s = np.frombuffer(bytes(seed), dtype=np.uint8).copy() if seed is not None else None
+        # (a proof without log2 N rounds goes in as identities: the verdicts are always wanted then)
+        out = np.zeros(max(n, 1), dtype=np.uint8) if locate or not all(good) else None
+        res = ctypes.c_int()
+        check(lib().vc_ipa_verify_batch(self.engine.h, self.table, self.N, n, *ptr, self._handles(transcripts, n),
+                                        _p(s) if s is not None else None, ctypes.byref(res),
+                                        _p(out) if out is not None else None), "ipa_verify_batch")
+        ok = bool(res.value) and all(good)
+        if locate:
+            return ok, [bool(v) and g for v, g in zip(out[:n], good)]
+        return ok
+
     def prove_commitment(self, commitment, data):
         """:199-234 -> IPAProof with l, r, tip (y = 0)."""
         return self.prove_commitment_batch([commitment], [data])[0]
@@ -478,6 +541,16 @@ def kzg_batch_challenge(seed):
     s = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
     out = np.zeros(4, dtype=np.uint64)
     check(lib().vc_kzg_batch_challenge(_p(s), _p(out)), "kzg_batch_challenge")
+    return limbs_to_int(out)
+
+
+def ipa_batch_challenge(seed):
+    """rho of vc_ipa_verify_batch for a 32-byte seed: hash_to_field(seed, b"vkzg-ipa-batch")."""
+    if len(seed) != 32:
+        raise ValueError("seed: 32 bytes")
+    s = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+    out = np.zeros(4, dtype=np.uint64)
+    check(lib().vc_ipa_batch_challenge(_p(s), _p(out)), "ipa_batch_challenge")
     return limbs_to_int(out)
 
 
