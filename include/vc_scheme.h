@@ -15,7 +15,8 @@
  *
  * Scope: the protocol layer is instantiated for BN254 (the only curve the reference runs,
  * vector-commit/Cargo.toml:15).  The MSM / commit engines (vc_msm.h) also serve BLS12-381 G1
- * and Bandersnatch.
+ * and Bandersnatch, and the KZG verifiers also take a BLS12-381 key (the section "KZG
+ * verification on BLS12-381" at the end states its layouts and rules).
  */
 #ifndef VC_SCHEME_H
 #define VC_SCHEME_H
@@ -344,6 +345,44 @@ int vc_multiproof_verify_kzg(vc_ctx* ctx, const vc_kzg_vk* vk, size_t N, size_t 
                              const uint8_t* com_inf, const uint64_t* z, const uint64_t* y, const uint64_t* d_xy,
                              uint8_t d_inf, const uint64_t* kzg_proof_xy, uint8_t kzg_proof_inf,
                              const uint64_t* kzg_y, int* result);
+
+/* ---------------------------------------------------------------- KZG verification on BLS12-381
+ * A verifying key has a curve: VC_CURVE_BN254 (every call above that takes no curve argument, as
+ * before) or VC_CURVE_BLS12_381 (csrc/pairing_bls.hpp: the ate pairing over the 64 bits of
+ * |x|, x = -0xd201000000010000). vc_kzg_verify, vc_kzg_verify_many, vc_kzg_batch_fold and
+ * vc_kzg_verify_batch dispatch on the key's curve; their contracts are the ones above with the
+ * BLS12-381 layouts below. A context whose curve is not the key's is VC_E_INVALID.
+ * vc_multiproof_verify_kzg and the verkle calls stay BN254: VC_E_INVALID for a BLS12-381 key.
+ *
+ * BLS12-381 layouts (canonical little-endian u64):
+ *   Fr   4 u64, below r.
+ *   G1   12 u64: x[6] y[6], below p, on y^2 = x^3 + 4 (vc_kzg_prove_many's 2 NL), plus a u8
+ *        identity flag. So com_xy / proof_xy are n x 12 and p1_xy / p2_xy are 12 u64.
+ *   G2   24 u64: x.c0[6] x.c1[6] y.c0[6] y.c1[6] (an Fq2 element is c0 + c1 u, u^2 = -1), on the
+ *        twist y^2 = x^3 + 4 (1 + u), plus a u8 identity flag.
+ * The domain generator is omega = 7^((r - 1) / size), vc_kzg_setup's for this curve.
+ *
+ * Status and verdict rules are the BN254 ones with one addition. G1 of BLS12-381 has a cofactor,
+ * and a point of E(Fq) outside the subgroup of order r pairs to one with every point of G2
+ * (pi + T, T of small order, would verify whenever pi does). So a G1 input that is on the curve
+ * but outside the subgroup is malformed, exactly as a point off the curve is: verdict 0 with VC_OK
+ * in vc_kzg_verify / vc_kzg_verify_many, *malformed = 1 in vc_kzg_batch_fold, *result = 0 with
+ * VC_OK in vc_kzg_verify_batch, VC_E_INVALID in vc_bls12_381_pairing_check. The test is
+ * phi^2(P) + [x^2] P == O, the one the MSM runs over whole tables; it is complete. The identity
+ * flag is a valid input and is not tested; flagged coordinates are not read.
+ * A malformed key ([s]_2 with a coordinate >= p, off the twist, outside the subgroup of order r,
+ * or the identity) is VC_E_INVALID, as is a curve other than the two above. */
+/* [secret]_2 = secret * H on the curve (H: its standard G2 generator); secret below the curve's r */
+int vc_kzg_g2_from_secret_curve(int curve, const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf);
+/* vc_kzg_vk_new for the curve; g2_xy in the curve's G2 layout (16 or 24 u64) */
+int vc_kzg_vk_new_curve(int curve, const uint64_t* g2_xy, uint8_t g2_inf, size_t size, vc_kzg_vk** vk);
+/* vc_kzg_batch_challenge for the curve: hash_to_field(seed, dst = "vkzg-kzg-batch") reduced mod
+ * the curve's r (48 expanded bytes for both curves) */
+int vc_kzg_batch_challenge_curve(int curve, const uint8_t seed[32], uint64_t* rho_fr);
+/* vc_bn254_pairing_check's contract on BLS12-381 (g1_xy n x 12, g2_xy n x 24 u64): VC_E_INVALID
+ * also for a G1 input outside the subgroup */
+int vc_bls12_381_pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                               const uint8_t* g2_inf, int* result);
 
 #ifdef __cplusplus
 }

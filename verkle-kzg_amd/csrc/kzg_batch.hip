@@ -29,6 +29,7 @@
 #include "ec29.hpp"
 #include "host/pool.hpp"
 #include "kzg_batch.hpp"
+#include "pairing_bls_entry.hpp"
 #include "pairing_internal.hpp"
 #include "scheme_internal.hpp"
 
@@ -221,10 +222,19 @@ extern "C" int vc_kzg_batch_challenge(const uint8_t seed[32], uint64_t* rho_fr) 
     return VC_OK;
 }
 
+extern "C" int vc_kzg_batch_challenge_curve(int curve, const uint8_t seed[32], uint64_t* rho_fr) {
+    if (curve == VC_CURVE_BN254) return vc_kzg_batch_challenge(seed, rho_fr);
+    if (curve == VC_CURVE_BLS12_381) return blsk::batch_challenge(seed, rho_fr);
+    return VC_E_INVALID;
+}
+
 extern "C" int vc_kzg_batch_fold(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint64_t* com_xy,
                                  const uint8_t* com_inf, const uint64_t* points, const uint64_t* proof_xy,
                                  const uint8_t* proof_inf, const uint64_t* y, const uint64_t* rho_fr, uint64_t* p1_xy,
                                  uint8_t* p1_inf, uint64_t* p2_xy, uint8_t* p2_inf, int* malformed) {
+    if (vk && vk->curve == VC_CURVE_BLS12_381)  // the key's curve decides (kzg_batch_bls.hip)
+        return blsk::batch_fold(ctx, vk, n, com_xy, com_inf, points, proof_xy, proof_inf, y, rho_fr, p1_xy, p1_inf,
+                                p2_xy, p2_inf, malformed);
     const Batch b{vk, n, com_xy, points, proof_xy, y, com_inf, proof_inf};
     if (!args_ok(ctx, b) || !rho_fr || !p1_xy || !p1_inf || !p2_xy || !p2_inf || !malformed) return VC_E_INVALID;
     if (!bn::words_below_modulus<BN254Fr>(w32(rho_fr))) return VC_E_INVALID;
@@ -248,6 +258,8 @@ extern "C" int vc_kzg_verify_batch(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, c
                                    const uint8_t* com_inf, const uint64_t* points, const uint64_t* proof_xy,
                                    const uint8_t* proof_inf, const uint64_t* y, const uint8_t* seed32, int* result,
                                    uint8_t* results) {
+    if (vk && vk->curve == VC_CURVE_BLS12_381)
+        return blsk::verify_batch(ctx, vk, n, com_xy, com_inf, points, proof_xy, proof_inf, y, seed32, result, results);
     const Batch b{vk, n, com_xy, points, proof_xy, y, com_inf, proof_inf};
     if (!args_ok(ctx, b) || !result || (results && !ctx)) return VC_E_INVALID;
     *result = 1;

@@ -1,12 +1,12 @@
-// Batched KZG verification on the GPU (vc_kzg_verify_many): one lane per opening, one verdict
-// per opening. A lane validates its inputs (Fr values below r, G1 coordinates below p and on the
-// curve), maps its point (omega^point below the domain size), forms A = y G - C - p pi, runs the
-// two-pairing Miller loop over the key's tabulated lines on (pi, [s]_2) and (A, H) with one
-// accumulator, the final exponentiation, and writes one byte. The arithmetic is csrc/pairing.hpp,
-// the text the host verifier runs (pairing_host.cpp). A key's tables stay in the context (22.5 KB)
-// until the context is destroyed.
+// Batched KZG verification on the GPU for a BLS12-381 key (vc_kzg_verify_many's dispatch): one lane
+// per opening, one verdict per opening. A lane validates its inputs (Fr values below r, G1
+// coordinates below p, on the curve and in the subgroup of order r), maps its point (omega^point
+// below the domain size), forms A = y G - C - p pi, runs the two-pairing Miller loop over the key's
+// tabulated lines on (pi, [s]_2) and (A, H) with one accumulator, the final exponentiation, and
+// writes one byte. The arithmetic is csrc/pairing_bls.hpp, the text the host verifier runs
+// (pairing_bls_host.cpp). A key's tables stay in the context (26 KB) until the context is destroyed.
 //
-// Shape: an Fq12 is 96 words and the loops hold several, so the kernel is declared for one wave
+// Shape: an Fq12 is 144 words and the loops hold several, so the kernel is declared for one wave
 // per SIMD (the whole unified VGPR + AGPR file for a lane) rather than squeezed to fit two. The
 // tower's multiplies are out-of-line functions with one copy each and the loops are rolled, so
 // the code stays small; nothing recurses, and the stack is static.
@@ -14,22 +14,20 @@
 
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <string>
-#include <vector>
 
 #include "ctx.hpp"
-#include "pairing_bls_entry.hpp"
+#include "pairing_bls_internal.hpp"
 #include "pairing_internal.hpp"
 
 namespace vk {
 
-using namespace bn;
+using namespace bls;
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_kzg_verify(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_kzg_verify_bls(
     const uint32_t* __restrict__ com_xy, const uint8_t* __restrict__ com_inf, const uint32_t* __restrict__ proof_xy,
     const uint8_t* __restrict__ proof_inf, const uint32_t* __restrict__ y, const uint32_t* __restrict__ points,
-    fe<BN254Fr> omega, uint64_t size, const LineCoef* __restrict__ lines, size_t n, uint8_t* __restrict__ out) {
+    FrE omega, uint64_t size, const LineCoef* __restrict__ lines, size_t n, uint8_t* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint8_t res = 0;
@@ -38,17 +36,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         yw[k] = y[8 * i + k];
         pt[k] = points[8 * i + k];
     }
-    if (words_below_modulus<BN254Fr>(yw) && words_below_modulus<BN254Fr>(pt)) {
+    if (words_below_modulus<BLS381Fr>(yw) && words_below_modulus<BLS381Fr>(pt)) {
         const bool c_inf = com_inf[i] != 0, pi_inf = proof_inf[i] != 0;
-        G1P C{fe_zero<BN254Fq>(), fe_zero<BN254Fq>()}, pi = C;
-        uint32_t w[16];
+        G1P C{fe_zero<BLS381Fq>(), fe_zero<BLS381Fq>()}, pi = C;
+        uint32_t w[2 * NL];
         bool ok = true;
         if (!c_inf) {
-            for (int k = 0; k < 16; k++) w[k] = com_xy[16 * i + k];
+            for (int k = 0; k < 2 * NL; k++) w[k] = com_xy[2 * NL * i + k];
             ok = g1_load(w, C);
         }
         if (ok && !pi_inf) {
-            for (int k = 0; k < 16; k++) w[k] = proof_xy[16 * i + k];
+            for (int k = 0; k < 2 * NL; k++) w[k] = proof_xy[2 * NL * i + k];
             ok = g1_load(w, pi);
         }
         if (ok) {
@@ -66,8 +64,8 @@ int cached_lines(vc_ctx* ctx, const vc_kzg_vk* vk, const LineCoef** out) {
     auto& slot = ctx->dcache["kzg_vk:" + std::to_string(vk->uid)];
     if (!slot) {
         auto b = std::make_unique<DevBuf>();
-        VK_TRY(b->ensure(sizeof vk->lines));
-        VK_CHECK_HIP(hipMemcpyAsync(b->p, vk->lines, sizeof vk->lines, hipMemcpyHostToDevice, ctx->stream));
+        VK_TRY(b->ensure(sizeof vk->bls->lines));
+        VK_CHECK_HIP(hipMemcpyAsync(b->p, vk->bls->lines, sizeof vk->bls->lines, hipMemcpyHostToDevice, ctx->stream));
         VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
         slot = std::move(b);
     }
@@ -76,39 +74,37 @@ int cached_lines(vc_ctx* ctx, const vc_kzg_vk* vk, const LineCoef** out) {
 }
 }  // namespace
 
-}  // namespace vk
-
-using namespace vk;
-
-extern "C" int vc_kzg_verify_many(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint64_t* com_xy,
-                                  const uint8_t* com_inf, const uint64_t* points, const uint64_t* proof_xy,
-                                  const uint8_t* proof_inf, const uint64_t* y, uint8_t* results) {
-    if (vk && vk->curve == VC_CURVE_BLS12_381)  // the key's curve decides (pairing_bls.hip)
-        return blsk::verify_many(ctx, vk, n, com_xy, com_inf, points, proof_xy, proof_inf, y, results);
-    if (!ctx || !vk || ctx->curve != VC_CURVE_BN254) return VC_E_INVALID;
+int blsk::verify_many(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint64_t* com_xy, const uint8_t* com_inf,
+                      const uint64_t* points, const uint64_t* proof_xy, const uint8_t* proof_inf, const uint64_t* y,
+                      uint8_t* results) {
+    if (!ctx || !vk || !vk->bls || ctx->curve != VC_CURVE_BLS12_381) return VC_E_INVALID;
     if (n && (!com_xy || !com_inf || !points || !proof_xy || !proof_inf || !y || !results)) return VC_E_INVALID;
     Guard g(ctx);
     if (n == 0) return VC_OK;
     const LineCoef* d_lines = nullptr;
     VK_TRY(cached_lines(ctx, vk, &d_lines));
+    constexpr size_t PB = 2 * NL * 4;  // bytes of a G1 point
     DevBuf dcom(ctx), dproof(ctx), dy(ctx), dp(ctx), dflags(ctx), dout(ctx);  // dp: the points
-    VK_TRY(dcom.ensure(n * 64));
-    VK_TRY(dproof.ensure(n * 64));
+    VK_TRY(dcom.ensure(n * PB));
+    VK_TRY(dproof.ensure(n * PB));
     VK_TRY(dy.ensure(n * 32));
     VK_TRY(dp.ensure(n * 32));
     VK_TRY(dflags.ensure(2 * n));
     VK_TRY(dout.ensure(n));
     uint8_t* fl = dflags.as<uint8_t>();
     hipStream_t st = ctx->stream;
-    VK_CHECK_HIP(hipMemcpyAsync(dcom.p, com_xy, n * 64, hipMemcpyHostToDevice, st));
-    VK_CHECK_HIP(hipMemcpyAsync(dproof.p, proof_xy, n * 64, hipMemcpyHostToDevice, st));
+    VK_CHECK_HIP(hipMemcpyAsync(dcom.p, com_xy, n * PB, hipMemcpyHostToDevice, st));
+    VK_CHECK_HIP(hipMemcpyAsync(dproof.p, proof_xy, n * PB, hipMemcpyHostToDevice, st));
     VK_CHECK_HIP(hipMemcpyAsync(dy.p, y, n * 32, hipMemcpyHostToDevice, st));
     VK_CHECK_HIP(hipMemcpyAsync(dp.p, points, n * 32, hipMemcpyHostToDevice, st));
     VK_CHECK_HIP(hipMemcpyAsync(fl, com_inf, n, hipMemcpyHostToDevice, st));
     VK_CHECK_HIP(hipMemcpyAsync(fl + n, proof_inf, n, hipMemcpyHostToDevice, st));
-    VK_LAUNCH(ctx, "kzg_verify", k_kzg_verify, (n + 63) / 64, 64, 0, dcom.as<uint32_t>(), fl, dproof.as<uint32_t>(),
-              fl + n, dy.as<uint32_t>(), dp.as<uint32_t>(), vk->omega, (uint64_t)vk->size, d_lines, n, dout.as<uint8_t>());
+    VK_LAUNCH(ctx, "kzg_verify_bls", k_kzg_verify_bls, (n + 63) / 64, 64, 0, dcom.as<uint32_t>(), fl,
+              dproof.as<uint32_t>(), fl + n, dy.as<uint32_t>(), dp.as<uint32_t>(), vk->bls->omega, (uint64_t)vk->size,
+              d_lines, n, dout.as<uint8_t>());
     VK_CHECK_HIP(hipMemcpyAsync(results, dout.p, n, hipMemcpyDeviceToHost, st));
     VK_CHECK_HIP(hipStreamSynchronize(st));
     return VC_OK;
 }
+
+}  // namespace vk

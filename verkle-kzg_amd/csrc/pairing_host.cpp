@@ -1,6 +1,7 @@
 // Host side of KZG verification (include/vc_scheme.h): the verifying key with its tabulated
 // Miller-loop lines, verify_point for one opening, the general pairing-product check. Pure host
-// code over csrc/pairing.hpp: no context, no GPU.
+// code over csrc/pairing.hpp: no context, no GPU. A BLS12-381 key or curve argument goes to
+// pairing_bls_host.cpp (vk::blsk); everything without a curve argument means BN254.
 #include <atomic>
 #include <cstring>
 #include <new>
@@ -8,6 +9,7 @@
 
 #include "../../include/vc_scheme.h"
 #include "kzg_batch.hpp"
+#include "pairing_bls_entry.hpp"
 #include "pairing_internal.hpp"
 
 using namespace vk;
@@ -41,8 +43,11 @@ bool fr_words(const uint64_t* fr, uint32_t* w) {  // canonical words; false when
     memcpy(w, fr, 32);
     return words_below_modulus<BN254Fr>(w);
 }
+bool is_bls(const vc_kzg_vk* vk) { return vk && vk->curve == VC_CURVE_BLS12_381; }
 
 }  // namespace
+
+int vk::kzg_vk_curve(const vc_kzg_vk* vk) { return vk->curve; }
 
 bool vk::kzg_pair_check(const vc_kzg_vk* vk, const G1A& P1, const G1A& P2) {
     return kzgb::pair_check(P1, P2, vk->lines, vk->lines + PC::ATE_LINES);
@@ -57,27 +62,55 @@ int vc_kzg_g2_from_secret(const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_
     return VC_OK;
 }
 
-int vc_kzg_vk_new(const uint64_t* g2_xy, uint8_t g2_inf, size_t size, vc_kzg_vk** out) {
+int vc_kzg_g2_from_secret_curve(int curve, const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf) {
+    if (curve == VC_CURVE_BN254) return vc_kzg_g2_from_secret(secret_fr, out_g2_xy, out_g2_inf);
+    if (curve == VC_CURVE_BLS12_381) return blsk::g2_from_secret(secret_fr, out_g2_xy, out_g2_inf);
+    return VC_E_INVALID;
+}
+
+int vc_kzg_vk_new_curve(int curve, const uint64_t* g2_xy, uint8_t g2_inf, size_t size, vc_kzg_vk** out) {
+    if (curve != VC_CURVE_BN254 && curve != VC_CURVE_BLS12_381) return VC_E_INVALID;
     if (!g2_xy || !out || size == 0 || (size & (size - 1)) || size > (size_t(1) << 28)) return VC_E_INVALID;
-    G2Aff s2;
-    if (g2_inf || !g2_load(g2_xy, false, s2) || !g2_on_twist(s2) || !g2_in_subgroup(s2)) return VC_E_INVALID;
+    G2Aff s2{fq2_zero(), fq2_zero(), true};
+    vc_kzg_vk_bls* tables = nullptr;
+    if (curve == VC_CURVE_BN254) {
+        if (g2_inf || !g2_load(g2_xy, false, s2) || !g2_on_twist(s2) || !g2_in_subgroup(s2)) return VC_E_INVALID;
+    } else {
+        const int st = blsk::vk_tables_new(g2_xy, g2_inf, size, &tables);
+        if (st != VC_OK) return st;
+    }
     vc_kzg_vk* vk = new (std::nothrow) vc_kzg_vk();
-    if (!vk) return VC_E_OOM;
-    static std::atomic<uint64_t> next_uid{1};
+    if (!vk) {
+        blsk::vk_tables_free(tables);
+        return VC_E_OOM;
+    }
+    static std::atomic<uint64_t> next_uid{1};  // one sequence for both curves: the contexts' cache key
     vk->uid = next_uid.fetch_add(1);
     vk->size = size;
-    vk->omega = bn254_group_gen(size);
-    vk->s2 = s2;
-    ate_line_table(s2, vk->lines);
-    ate_line_table(g2_generator(), vk->lines + PC::ATE_LINES);
+    vk->curve = curve;
+    vk->bls = tables;
+    if (curve == VC_CURVE_BN254) {
+        vk->omega = bn254_group_gen(size);
+        vk->s2 = s2;
+        ate_line_table(s2, vk->lines);
+        ate_line_table(g2_generator(), vk->lines + PC::ATE_LINES);
+    }
     *out = vk;
     return VC_OK;
 }
 
-void vc_kzg_vk_free(vc_kzg_vk* vk) { delete vk; }
+int vc_kzg_vk_new(const uint64_t* g2_xy, uint8_t g2_inf, size_t size, vc_kzg_vk** out) {
+    return vc_kzg_vk_new_curve(VC_CURVE_BN254, g2_xy, g2_inf, size, out);
+}
+
+void vc_kzg_vk_free(vc_kzg_vk* vk) {
+    if (vk) blsk::vk_tables_free(vk->bls);
+    delete vk;
+}
 
 int vc_kzg_verify(const vc_kzg_vk* vk, const uint64_t* com_xy, uint8_t com_inf, const uint64_t* point_fr,
                   const uint64_t* proof_xy, uint8_t proof_inf, const uint64_t* y_fr, int* result) {
+    if (is_bls(vk)) return blsk::verify(vk, com_xy, com_inf, point_fr, proof_xy, proof_inf, y_fr, result);
     if (!vk || (!com_xy && !com_inf) || !point_fr || (!proof_xy && !proof_inf) || !y_fr || !result) return VC_E_INVALID;
     *result = 0;
     uint32_t y[8], pt[8], w[16];
@@ -115,6 +148,11 @@ int vc_bn254_pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_in
     }
     *result = pairing_product_is_one((int)n, P.data(), Q.data()) ? 1 : 0;
     return VC_OK;
+}
+
+int vc_bls12_381_pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                               const uint8_t* g2_inf, int* result) {
+    return blsk::pairing_check(n, g1_xy, g1_inf, g2_xy, g2_inf, result);
 }
 
 }  // extern "C"

@@ -2400,6 +2400,7 @@ int vc_multiproof_verify_kzg(vc_ctx* ctx, const vc_kzg_vk* vk, size_t N, size_t 
                              uint8_t d_inf, const uint64_t* kzg_proof_xy, uint8_t kzg_proof_inf,
                              const uint64_t* kzg_y, int* result) {
     if (!vk || !result || !kzg_y || (!kzg_proof_xy && !kzg_proof_inf)) return VC_E_INVALID;
+    if (kzg_vk_curve(vk) != VC_CURVE_BN254) return VC_E_INVALID;  // the protocol layer is BN254
     uint64_t c_xy[8], t[4];
     uint8_t c_inf = 0;
     VK_TRY(vc_multiproof_kzg_claim(ctx, N, Q, com_xy, com_inf, z, y, d_xy, d_inf, c_xy, &c_inf, t));

@@ -22,6 +22,7 @@ uint8_t* transcript_extend(vc_transcript* t, size_t n);
 using RecordFill = std::function<void(size_t lo, size_t hi, uint8_t* out)>;
 Fr transcript_digest_records(vc_transcript* t, size_t nrec, size_t rec, const RecordFill& fill, const char* label,
                              bool pool_ok);
+int kzg_vk_curve(const vc_kzg_vk* vk);  // the key's curve (pairing_host.cpp)
 Fr to_data_item_host(const uint64_t* xy, bool inf);
 // [w, x_0 .. x_{K-1}] (Montgomery) of entries [lo, lo + cnt) of vc_ipa_verify_many's arrays into
 // chal[0 .. cnt (K + 1)), on the host pool; transcripts: NULL, or handles indexed by entry (NULL:

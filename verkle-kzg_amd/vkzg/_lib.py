@@ -126,6 +126,10 @@ SIGNATURES = {
     "vc_bn254_pairing_check": (c_int, [c_size_t, P, P, P, P, ctypes.POINTER(c_int)]),
     "vc_kzg_verify_many": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P]),
     "vc_kzg_batch_challenge": (c_int, [P, P]),
+    "vc_kzg_g2_from_secret_curve": (c_int, [c_int, P, P, P]),
+    "vc_kzg_vk_new_curve": (c_int, [c_int, P, ctypes.c_uint8, c_size_t, ctypes.POINTER(c_void_p)]),
+    "vc_kzg_batch_challenge_curve": (c_int, [c_int, P, P]),
+    "vc_bls12_381_pairing_check": (c_int, [c_size_t, P, P, P, P, ctypes.POINTER(c_int)]),
     "vc_kzg_batch_fold": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P, P, P, P, P,
                                   ctypes.POINTER(c_int)]),
     "vc_kzg_verify_batch": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P, ctypes.POINTER(c_int), P]),

@@ -5,7 +5,9 @@ Mirrors /root/reference/vector-commit/src: `IPA` (ipa/mod.rs), `KZG` (kzg/mod.rs
 `prove_multiproof` / `verify_multiproof` / `verify_multiproof_kzg` (multiproof.rs), `to_data_item`
 (lib.rs:56-67). KZG openings are verified with pairings through `KZGVerifyingKey`.
 Same names, argument meaning and error behaviour (errors raise `VCError` where the Rust
-returns Err or panics). Curve: BN254 G1 (the reference's only instantiation).
+returns Err or panics). Curve: BN254 G1 (the reference's only instantiation); `KZG`,
+`KZGVerifyingKey`, `kzg_g2_from_secret`, `kzg_batch_challenge` and `pairing_check` also work on
+BLS12-381 (an `Engine("bls12_381")` / `curve="bls12_381"`; G1 coordinates are then 6 u64 limbs).
 Points are canonical affine (x, y) tuples, the identity is None; field elements are ints.
 All arithmetic runs in libvkzg.so; this module only marshals.
 """
@@ -17,7 +19,16 @@ from ._lib import VCError, check, lib
 from .engine import Engine, ints_to_limbs, limbs_to_int
 
 R_BN254 = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+R_BLS12_381 = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 _P = ctypes.c_void_p
+# the curves with a pairing: scalar field, u64 limbs of a base-field coordinate, the ABI's curve id
+_PAIRING_CURVES = {"bn254": (R_BN254, 4, 0), "bls12_381": (R_BLS12_381, 6, 1)}
+
+
+def _curve_params(curve):
+    if curve not in _PAIRING_CURVES:
+        raise ValueError(f"no pairing on curve {curve!r}")
+    return _PAIRING_CURVES[curve]
 
 
 def _p(a):
@@ -28,26 +39,29 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-def _fr(x):
-    return ints_to_limbs([int(x) % R_BN254], 4)[0].copy()
+def _fr(x, r=R_BN254):
+    return ints_to_limbs([int(x) % r], 4)[0].copy()
 
 
 _M256 = (1 << 256) - 1
 
 
-def _pt_arrays(pts):
-    """[(x, y) | None] -> ((n, 8) u64 limbs, (n,) identity flags): one bytes buffer for all points
-    (per-point numpy assignments cost ~10 us per call of the IPA prover's Python mirror)"""
+def _pt_arrays(pts, nl=4):
+    """[(x, y) | None] -> ((n, 2 nl) u64 limbs, (n,) identity flags): one bytes buffer for all points
+    (per-point numpy assignments cost ~10 us per call of the IPA prover's Python mirror). nl: u64
+    limbs of a coordinate (4: BN254, 6: BLS12-381)"""
     n = len(pts)
-    buf = bytearray(64 * n)
+    cb = 8 * nl
+    mask = (1 << (8 * cb)) - 1
+    buf = bytearray(2 * cb * n)
     inf = np.zeros(n, dtype=np.uint8)
     for i, P in enumerate(pts):
         if P is None:
             inf[i] = 1
         else:
-            buf[64 * i:64 * i + 32] = (int(P[0]) & _M256).to_bytes(32, "little")
-            buf[64 * i + 32:64 * i + 64] = (int(P[1]) & _M256).to_bytes(32, "little")
-    xy = np.frombuffer(buf, dtype="<u8").reshape(n, 8).astype(np.uint64)
+            buf[2 * cb * i:2 * cb * i + cb] = (int(P[0]) & mask).to_bytes(cb, "little")
+            buf[2 * cb * i + cb:2 * cb * (i + 1)] = (int(P[1]) & mask).to_bytes(cb, "little")
+    xy = np.frombuffer(buf, dtype="<u8").reshape(n, 2 * nl).astype(np.uint64)
     return xy, inf
 
 
@@ -65,7 +79,8 @@ def _pt_arrays_many(pts):
 def _pt(xy, inf):
     if inf:
         return None
-    return (limbs_to_int(xy[:4]), limbs_to_int(xy[4:8]))
+    nl = len(xy) // 2
+    return (limbs_to_int(xy[:nl]), limbs_to_int(xy[nl:2 * nl]))
 
 
 # ---------------------------------------------------------------- transcript.rs
@@ -132,9 +147,9 @@ def ipa_crs(num, seed=b"eth_verkle_oct_2021", max_=256):
 class LagrangeBasis:
     """Evaluations over a radix-2 domain (possibly shorter than it: `max`)."""
 
-    def __init__(self, evals, domain_size=None):
+    def __init__(self, evals, domain_size=None, r=R_BN254):
         # a tuple: the limbs below are cached per padded length, so the values must not change
-        self.evals = tuple(int(e) % R_BN254 for e in evals)
+        self.evals = tuple(int(e) % r for e in evals)
         self._limbs = {}
         ds = 1
         while ds < len(self.evals):
@@ -412,52 +427,59 @@ def _fr_raw(x):
     return ints_to_limbs([int(x) & _M256], 4)[0].copy()
 
 
-def _g2_array(Q):
-    """((x0, x1), (y0, y1)) | None -> (16 u64 limbs, identity flag) in the ABI's G2 layout"""
-    xy = np.zeros(16, dtype=np.uint64)
+def _g2_array(Q, nl=4):
+    """((x0, x1), (y0, y1)) | None -> (4 nl u64 limbs, identity flag) in the ABI's G2 layout"""
+    xy = np.zeros(4 * nl, dtype=np.uint64)
     if Q is None:
         return xy, 1
     (x0, x1), (y0, y1) = Q
-    xy[:] = ints_to_limbs([int(v) & _M256 for v in (x0, x1, y0, y1)], 4).reshape(16)
+    mask = (1 << (64 * nl)) - 1
+    xy[:] = ints_to_limbs([int(v) & mask for v in (x0, x1, y0, y1)], nl).reshape(4 * nl)
     return xy, 0
 
 
-def kzg_g2_from_secret(secret):
+def kzg_g2_from_secret(secret, curve="bn254"):
     """[secret]_2 = secret * H (kzg/mod.rs:122) as ((x.c0, x.c1), (y.c0, y.c1)), None = identity."""
-    xy = np.zeros(16, dtype=np.uint64)
+    r, nl, cid = _curve_params(curve)
+    xy = np.zeros(4 * nl, dtype=np.uint64)
     inf = np.zeros(1, dtype=np.uint8)
-    check(lib().vc_kzg_g2_from_secret(_p(_fr(secret)), _p(xy), _p(inf)), "kzg_g2_from_secret")
+    check(lib().vc_kzg_g2_from_secret_curve(cid, _p(_fr(secret, r)), _p(xy), _p(inf)), "kzg_g2_from_secret")
     if inf[0]:
         return None
-    v = [limbs_to_int(xy[4 * k:4 * k + 4]) for k in range(4)]
+    v = [limbs_to_int(xy[nl * k:nl * k + nl]) for k in range(4)]
     return ((v[0], v[1]), (v[2], v[3]))
 
 
-def pairing_check(pairs):
+def pairing_check(pairs, curve="bn254"):
     """prod e(P_i, Q_i) == 1 for pairs of (G1 point | None, G2 point | None); VCError for an
-    input off its curve or a G2 point outside the subgroup. Host code."""
+    input off its curve or outside its subgroup. Host code."""
+    _, nl, _ = _curve_params(curve)
     n = len(pairs)
-    g1, g1inf = _pt_arrays([a for a, _ in pairs]) if n else (np.zeros((1, 8), dtype=np.uint64), np.zeros(1, dtype=np.uint8))
-    g2 = np.zeros((max(n, 1), 16), dtype=np.uint64)
+    g1, g1inf = (_pt_arrays([a for a, _ in pairs], nl) if n
+                 else (np.zeros((1, 2 * nl), dtype=np.uint64), np.zeros(1, dtype=np.uint8)))
+    g2 = np.zeros((max(n, 1), 4 * nl), dtype=np.uint64)
     g2inf = np.zeros(max(n, 1), dtype=np.uint8)
     for i, (_, Q) in enumerate(pairs):
-        g2[i], g2inf[i] = _g2_array(Q)
+        g2[i], g2inf[i] = _g2_array(Q, nl)
     res = ctypes.c_int()
-    check(lib().vc_bn254_pairing_check(n, _p(g1), _p(g1inf), _p(g2), _p(g2inf), ctypes.byref(res)), "pairing_check")
+    fn = lib().vc_bn254_pairing_check if curve == "bn254" else lib().vc_bls12_381_pairing_check
+    check(fn(n, _p(g1), _p(g1inf), _p(g2), _p(g2inf), ctypes.byref(res)), "pairing_check")
     return bool(res.value)
 
 
 class KZGVerifyingKey:
     """[s]_2 and the domain size: all KZG::verify_point needs (no SRS, no secret). Host code
     except verify_many, and verify_batch / batch_fold when given an Engine. VCError(VC_E_INVALID)
-    for a malformed [s]_2."""
+    for a malformed [s]_2. curve: "bn254" or "bls12_381"; an Engine given to verify_many /
+    verify_batch / batch_fold must be of the key's curve."""
 
-    def __init__(self, g2, size):
-        xy, inf = _g2_array(g2)
-        h = ctypes.c_void_p()
+    def __init__(self, g2, size, curve="bn254"):
         self.h = None
-        check(lib().vc_kzg_vk_new(_p(xy), inf, size, ctypes.byref(h)), "kzg_vk_new")
-        self.h, self.size, self.g2 = h, size, g2
+        self.r, self.nl, cid = _curve_params(curve)
+        xy, inf = _g2_array(g2, self.nl)
+        h = ctypes.c_void_p()
+        check(lib().vc_kzg_vk_new_curve(cid, _p(xy), inf, size, ctypes.byref(h)), "kzg_vk_new")
+        self.h, self.size, self.g2, self.curve = h, size, g2, curve
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -466,8 +488,8 @@ class KZGVerifyingKey:
 
     def verify_point(self, commitment, point, proof, transcript=None):
         """:165-189; proof = {"proof": point, "y": int}. The transcript is unused, as in the reference."""
-        cxy, cinf = _pt_arrays([commitment])
-        pxy, pinf = _pt_arrays([proof["proof"]])
+        cxy, cinf = _pt_arrays([commitment], self.nl)
+        pxy, pinf = _pt_arrays([proof["proof"]], self.nl)
         res = ctypes.c_int()
         check(lib().vc_kzg_verify(self.h, _p(cxy), int(cinf[0]), _p(_fr_raw(point)), _p(pxy), int(pinf[0]),
                                   _p(_fr_raw(proof["y"])), ctypes.byref(res)), "kzg_verify")
@@ -481,8 +503,8 @@ class KZGVerifyingKey:
         n = len(proofs)
         if n == 0:
             return []
-        cxy, cinf = _pt_arrays(commitments)
-        pxy, pinf = _pt_arrays([pr["proof"] for pr in proofs])
+        cxy, cinf = _pt_arrays(commitments, self.nl)
+        pxy, pinf = _pt_arrays([pr["proof"] for pr in proofs], self.nl)
         pts = ints_to_limbs([int(p) & _M256 for p in points], 4)
         ys = ints_to_limbs([int(pr["y"]) & _M256 for pr in proofs], 4)
         out = np.zeros(n, dtype=np.uint8)
@@ -491,8 +513,8 @@ class KZGVerifyingKey:
         return [bool(v) for v in out]
 
     def _batch_arrays(self, commitments, points, proofs):
-        cxy, cinf = _pt_arrays(commitments)
-        pxy, pinf = _pt_arrays([pr["proof"] for pr in proofs])
+        cxy, cinf = _pt_arrays(commitments, self.nl)
+        pxy, pinf = _pt_arrays([pr["proof"] for pr in proofs], self.nl)
         pts = ints_to_limbs([int(p) & _M256 for p in points], 4)
         ys = ints_to_limbs([int(pr["y"]) & _M256 for pr in proofs], 4)
         return cxy, cinf, pts, pxy, pinf, ys
@@ -503,7 +525,7 @@ class KZGVerifyingKey:
         n = len(proofs)
         a = self._batch_arrays(commitments, points, proofs) if n else (None,) * 6
         ptr = [_p(x) if x is not None else None for x in a]
-        out = np.zeros((2, 8), dtype=np.uint64)
+        out = np.zeros((2, 2 * self.nl), dtype=np.uint64)
         inf = np.zeros(2, dtype=np.uint8)
         bad = ctypes.c_int()
         check(lib().vc_kzg_batch_fold(engine.h if engine is not None else None, self.h, n, *ptr, _p(_fr_raw(rho)),
@@ -534,13 +556,15 @@ class KZGVerifyingKey:
         return bool(res.value)
 
 
-def kzg_batch_challenge(seed):
-    """rho of vc_kzg_verify_batch for a 32-byte seed: hash_to_field(seed, b"vkzg-kzg-batch")."""
+def kzg_batch_challenge(seed, curve="bn254"):
+    """rho of vc_kzg_verify_batch for a 32-byte seed: hash_to_field(seed, b"vkzg-kzg-batch") mod
+    the curve's r."""
     if len(seed) != 32:
         raise ValueError("seed: 32 bytes")
+    _, _, cid = _curve_params(curve)
     s = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
     out = np.zeros(4, dtype=np.uint64)
-    check(lib().vc_kzg_batch_challenge(_p(s), _p(out)), "kzg_batch_challenge")
+    check(lib().vc_kzg_batch_challenge_curve(cid, _p(s), _p(out)), "kzg_batch_challenge")
     return limbs_to_int(out)
 
 
@@ -555,13 +579,16 @@ def ipa_batch_challenge(seed):
 
 
 class KZG:
-    """KZG<Bn254, ...>: commit, open and (through KZGVerifyingKey) verify with pairings."""
+    """KZG<Bn254, ...>: commit, open and (through KZGVerifyingKey) verify with pairings. On an
+    Engine("bls12_381") the same over BLS12-381 (data: LagrangeBasis(evals, r=R_BLS12_381));
+    prove_all_points, quotient and the multiproofs stay BN254."""
 
     def __init__(self, engine, max_items, secret=100):
         self.engine = engine
+        self.r, self.nl, _ = _curve_params(engine.curve)
         tid = ctypes.c_int()
         size = ctypes.c_size_t()
-        check(lib().vc_kzg_setup(engine.h, max_items, _p(_fr(secret)), ctypes.byref(tid), ctypes.byref(size)),
+        check(lib().vc_kzg_setup(engine.h, max_items, _p(_fr(secret, self.r)), ctypes.byref(tid), ctypes.byref(size)),
               "kzg_setup")
         self.table, self.size, self.secret = tid.value, size.value, secret
 
@@ -580,10 +607,10 @@ class KZG:
 
     def prove_point(self, commitment, point, data, transcript=None):
         ev = data.limbs()
-        pxy = np.zeros(8, dtype=np.uint64)
+        pxy = np.zeros(2 * self.nl, dtype=np.uint64)
         pinf = np.zeros(1, dtype=np.uint8)
         y = np.zeros(4, dtype=np.uint64)
-        check(lib().vc_kzg_prove(self.engine.h, self.table, self.size, _p(ev), len(data.evals), _p(_fr(point)),
+        check(lib().vc_kzg_prove(self.engine.h, self.table, self.size, _p(ev), len(data.evals), _p(_fr(point, self.r)),
                                  _p(pxy), _p(pinf), _p(y)), "kzg_prove")
         return {"proof": _pt(pxy, pinf[0]), "y": limbs_to_int(y)}
 
@@ -603,11 +630,11 @@ class KZG:
             raise ValueError("one batch proves data of one length")
         ev = datas[0].limbs() if len(datas) == 1 else np.concatenate([d.limbs() for d in datas])
         ev = np.ascontiguousarray(ev)
-        pts = ints_to_limbs([int(p) % R_BN254 for p in points], 4)
+        pts = ints_to_limbs([int(p) % self.r for p in points], 4)
         row = np.ascontiguousarray(np.asarray(rows, dtype=np.uint32)) if rows is not None else None
         if row is not None and row.shape != (n,):
             raise ValueError("rows: one data index per point")
-        pxy = np.zeros((n, 8), dtype=np.uint64)
+        pxy = np.zeros((n, 2 * self.nl), dtype=np.uint64)
         pinf = np.zeros(n, dtype=np.uint8)
         ys = np.zeros((n, 4), dtype=np.uint64)
         check(lib().vc_kzg_prove_many(self.engine.h, self.table, self.size, len(datas), width, _p(ev),
@@ -631,11 +658,11 @@ class KZG:
 
     def g2(self):
         """[s]_2 of the setup (kzg/mod.rs:122)."""
-        return kzg_g2_from_secret(self.secret)
+        return kzg_g2_from_secret(self.secret, self.engine.curve)
 
     def verifying_key(self):
         if getattr(self, "_vk", None) is None:
-            self._vk = KZGVerifyingKey(self.g2(), self.size)
+            self._vk = KZGVerifyingKey(self.g2(), self.size, self.engine.curve)
         return self._vk
 
     def verify_point(self, commitment, point, proof, transcript=None):
