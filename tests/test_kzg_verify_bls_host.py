@@ -3,6 +3,9 @@ are the oracle's (tests/kzg_batch_bls_cases.py: verdicts from protocol.KZG.verif
 trapdoor, False for anything malformed, the fold in pyoracle.curves.BLS12_381 arithmetic, the
 challenge from arkser.hash_to_field; [s]_2 from tests/bls12_381_g2.py). Comparisons are exact."""
 import ctypes
+import json
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +16,7 @@ from pyoracle import arkser
 from pyoracle.curves import BLS12_381, BLS_P, BLS_R
 
 VC_E_INVALID = -1
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
@@ -135,6 +139,34 @@ def test_host_batch_rejects_tampered_and_reports_malformed(vk, rhos):
         assert vk.verify_batch(None, *cases.arrays(batch), seed=cases.SEEDS[0]) is False, name
     assert vk.verify_batch(None, [], [], []) is True
     _invalid(lambda: vk.batch_fold(None, *cases.arrays(cases.valid_batch(2)), BLS_R))
+
+
+def test_fold_and_pairing_entry_under_the_sanitizers(tmp_path, rhos):
+    """csrc/kzg_batch.hpp for BLS12-381 and the final pairing entry as a stand-alone program
+    (tests/cpp/kzg_batch_check.cpp with the curve as its second argument, built with g++ and the
+    address / undefined-behaviour sanitizers, run directly): valid batches of 1, 2 and 17, a batch
+    of 5 with a tampered entry, a batch of 5 with pi + T; expected points from the oracle's fold"""
+    from test_kzg_verify_batch_host import _dump
+    batches = []
+    for n, rho in ((1, rhos[0]), (2, rhos[1]), (17, rhos[2])):
+        batch = cases.valid_batch(n)
+        batches.append((batch, rho, False, True, cases.oracle_fold(batch, rho)))
+    batch = cases.valid_batch(5)
+    batch[3] = cases.tampered_pool()[0]
+    batches.append((batch, rhos[0], False, False, cases.oracle_fold(batch, rhos[0])))
+    batch = cases.valid_batch(5)
+    batch[2] = dict(cases.subgroup_cases())["subgroup_proof_plus_T"]
+    batches.append((batch, rhos[1], True, False, (None, None)))
+    flat = tmp_path / "batches.txt"
+    _dump(flat, cases.fixture(), batches)
+    exe = tmp_path / "kzg_batch_check"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                           os.path.join(HERE, "cpp", "kzg_batch_check.cpp"), "-o", str(exe)])
+    out = subprocess.check_output([str(exe), str(flat), cases.CURVE], text=True, timeout=600)
+    d = json.loads(out.splitlines()[-1])
+    print(d)
+    assert d == {"batches": 5, "wrong": 0, "accepted": 3, "rejected": 1, "malformed": 1, "pow_checks": 30}
 
 
 def test_a_bn254_key_is_still_bn254_whatever_the_array_sizes():

@@ -236,7 +236,7 @@ bool domain_error(const Batch& b) {
     std::atomic<bool> err{false};
     pool_for(0, b.n, 256, [&](size_t p) {
         uint64_t idx;
-        if (!bn::words_below_modulus<F>(w32(b.points + 4 * p))) return;
+        if (!ate::words_below_modulus<F>(w32(b.points + 4 * p))) return;
         if (point_in_domain(w32(b.points + 4 * p), b.N, &idx)) return;
         if (fe_eq<F>(fe_pow_u64<F>(canon_to_mont<F>(b.points + 4 * p), b.N), fe_one<F>())) err = true;
     });
@@ -419,7 +419,7 @@ int fold_host(const uint64_t* crs_xy, const Batch& b, const Fr& rho, const std::
     const size_t N = b.N, C = (size_t)b.K + 1;
     std::vector<G1P> crs(N + 1);
     for (size_t i = 0; i <= N; i++)
-        if (!bn::g1_load(w32(crs_xy + 8 * i), crs[i])) return VC_E_INVALID;
+        if (!ate::g1_load(w32(crs_xy + 8 * i), crs[i])) return VC_E_INVALID;
     const std::vector<Fr> pw = domain_powers(N);
     const Fr n_inv = fe_inv_bin<BN254Fr>(mont_from_u64<BN254Fr>(N));
     HostPool& pool = host_pool();
@@ -534,7 +534,7 @@ extern "C" int vc_ipa_batch_fold(vc_ctx* ctx, int table, const uint64_t* crs_xy,
                                  const uint64_t* rho_fr, uint64_t* s_xy, uint8_t* s_inf, int* malformed) {
     const Batch b{N, n, log2_of(N), com_xy, points, l_xy, r_xy, tip, y, com_inf, l_inf, r_inf, transcripts};
     if (!rho_fr || !s_xy || !s_inf || !malformed) return VC_E_INVALID;
-    if (!bn::words_below_modulus<BN254Fr>(w32(rho_fr))) return VC_E_INVALID;
+    if (!ate::words_below_modulus<BN254Fr>(w32(rho_fr))) return VC_E_INVALID;
     G1A S = BN254G1::zero();  // (n = 0: the sum is empty)
     bool bad = false;
     Laps laps;

@@ -220,13 +220,13 @@ VK_HD FrE pow_index(const FrE& rho, uint64_t e) {
 }
 // tip, y and the point canonical below r (vc_ipa_verify_many's field kernel calls the rest bad)
 VK_HD bool entry_fr_ok(const uint32_t* tip, const uint32_t* y, const uint32_t* point) {
-    return bn::words_below_modulus<BN254Fr>(tip) && bn::words_below_modulus<BN254Fr>(y) &&
-           bn::words_below_modulus<BN254Fr>(point);
+    return ate::words_below_modulus<BN254Fr>(tip) && ate::words_below_modulus<BN254Fr>(y) &&
+           ate::words_below_modulus<BN254Fr>(point);
 }
 // a point of an entry (canonical words, identity flag) in Montgomery form; false: malformed
 VK_HD bool point_load(const uint32_t* xy, bool inf, G1P& out) {
     out = G1P{fe_zero<BN254Fq>(), fe_zero<BN254Fq>()};
-    return inf || bn::g1_load(xy, out);
+    return inf || ate::g1_load(xy, out);
 }
 
 // One entry's share of the fold on one thread (the host path and the check program): row[0..N] +=

@@ -65,8 +65,8 @@ __global__ __launch_bounds__(64) void k_ipa_verify_field(const uint32_t* __restr
         zw[k] = point_w[8 * p + k];
     }
     uint32_t* row = rows + p * ((size_t)N + 1) * 8;
-    if (!(bn::words_below_modulus<BN254Fr>(tw) && bn::words_below_modulus<BN254Fr>(yw) &&
-          bn::words_below_modulus<BN254Fr>(zw))) {  // (uniform over the block)
+    if (!(ate::words_below_modulus<BN254Fr>(tw) && ate::words_below_modulus<BN254Fr>(yw) &&
+          ate::words_below_modulus<BN254Fr>(zw))) {  // (uniform over the block)
         for (size_t i = lane; i <= N; i += 64) fr_store(fe_zero<BN254Fr>(), row + 8 * i);
         if (lane == 0) bad[p] = 1;
         return;
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(64) void k_ipa_verify_curve(uint32_t* com_xy, const
             uint32_t w[16];
             for (int k = 0; k < 16; k++) w[k] = q[k];
             G1P P;
-            if (!bn::g1_load(w, P)) {
+            if (!ate::g1_load(w, P)) {
                 ok = 0;
                 break;
             }
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(64) void k_ipa_verify_curve(uint32_t* com_xy, const
 }
 
 namespace {
-bool canonical_fr(const uint64_t* w) { return bn::words_below_modulus<BN254Fr>(reinterpret_cast<const uint32_t*>(w)); }
+bool canonical_fr(const uint64_t* w) { return ate::words_below_modulus<BN254Fr>(reinterpret_cast<const uint32_t*>(w)); }
 }  // namespace
 
 // (shared with vc_ipa_verify_batch's prior-transcript path, ipa_batch.hip)

@@ -20,13 +20,13 @@
 // every scalar multiplied by B, and B <b, s> = t A needs no division. (A lone lane's Fermat
 // inversion, ~380 multiplies in series, cost more than the rest of the field phase together.)
 #pragma once
-#include "pairing.hpp"
+#include "pairing.hpp"  // the input checks: ate::words_below_modulus, ate::g1_load (also reachable as bn::)
 
 namespace vk {
 namespace ipav {
 
 // The group law and the multiplies are the engine's inlined ones (ec.hpp BN254G1, ff.hpp): the
-// kernels here hold one accumulator and one point, so unlike the pairing tower (pairing.hpp's
+// kernels here hold one accumulator and one point, so unlike the pairing tower (pairing_common.hpp's
 // out-of-line multiplies) they need no calls, and their operands stay in registers.
 using G1A = BN254G1::Acc;
 using G1P = BN254G1::Aff;

@@ -1,101 +1,151 @@
 // Host side of KZG verification (include/vc_scheme.h): the verifying key with its tabulated
 // Miller-loop lines, verify_point for one opening, the general pairing-product check. Pure host
-// code over csrc/pairing.hpp: no context, no GPU. A BLS12-381 key or curve argument goes to
-// pairing_bls_host.cpp (vk::blsk); everything without a curve argument means BN254.
+// code over pairing_common.hpp with pairing.hpp / pairing_bls.hpp: no context, no GPU. One text
+// for both curves (C: a curve of kzg_curves.hpp); a key's curve or the curve argument selects the
+// instantiation, and everything without a curve argument means BN254.
 #include <atomic>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/vc_scheme.h"
-#include "kzg_batch.hpp"
-#include "pairing_bls_entry.hpp"
+#include "host/fr.hpp"
 #include "pairing_internal.hpp"
 
 using namespace vk;
-using namespace vk::bn;
+using namespace vk::ate;
 
 namespace {
 
 // G2 in the ABI layout (x.c0 x.c1 y.c0 y.c1, canonical) -> Montgomery; false for a coordinate >= p
-bool g2_load(const uint64_t* xy, bool inf, G2Aff& out) {
-    out = G2Aff{fq2_zero(), fq2_zero(), inf};
+template <class F>
+bool g2_load(const uint64_t* xy, bool inf, G2AffT<F>& out) {
+    constexpr int NW = F::N / 2;  // u64 words of a coordinate
+    out = G2AffT<F>{fq2_zero<F>(), fq2_zero<F>(), inf};
     if (inf) return true;
-    Fq* dst[4] = {&out.x.c0, &out.x.c1, &out.y.c0, &out.y.c1};
+    fe<F>* dst[4] = {&out.x.c0, &out.x.c1, &out.y.c0, &out.y.c1};
     for (int k = 0; k < 4; k++) {
-        uint32_t w[8];
-        memcpy(w, xy + 4 * k, 32);
-        if (!words_below_modulus<BN254Fq>(w)) return false;
-        *dst[k] = canon_to_mont<BN254Fq>(xy + 4 * k);
+        uint32_t w[F::N];
+        memcpy(w, xy + NW * k, sizeof w);
+        if (!words_below_modulus<F>(w)) return false;
+        *dst[k] = canon_to_mont<F>(xy + NW * k);
     }
     return true;
 }
-void g2_store(const G2Aff& p, uint64_t* xy, uint8_t* inf) {
-    memset(xy, 0, 128);
+template <class F>
+void g2_store(const G2AffT<F>& p, uint64_t* xy, uint8_t* inf) {
+    constexpr int NW = F::N / 2;
+    memset(xy, 0, 8 * 4 * NW);
     *inf = p.inf ? 1 : 0;
     if (p.inf) return;
-    mont_to_canon<BN254Fq>(p.x.c0, xy);
-    mont_to_canon<BN254Fq>(p.x.c1, xy + 4);
-    mont_to_canon<BN254Fq>(p.y.c0, xy + 8);
-    mont_to_canon<BN254Fq>(p.y.c1, xy + 12);
+    mont_to_canon<F>(p.x.c0, xy);
+    mont_to_canon<F>(p.x.c1, xy + NW);
+    mont_to_canon<F>(p.y.c0, xy + 2 * NW);
+    mont_to_canon<F>(p.y.c1, xy + 3 * NW);
 }
+template <class Fr>
 bool fr_words(const uint64_t* fr, uint32_t* w) {  // canonical words; false when >= r
     memcpy(w, fr, 32);
-    return words_below_modulus<BN254Fr>(w);
+    return words_below_modulus<Fr>(w);
 }
-bool is_bls(const vc_kzg_vk* vk) { return vk && vk->curve == VC_CURVE_BLS12_381; }
+
+template <class C>
+int g2_from_secret(const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf) {
+    uint32_t s[8];
+    if (!secret_fr || !out_g2_xy || !out_g2_inf || !fr_words<typename C::Fr>(secret_fr, s)) return VC_E_INVALID;
+    g2_store(g2_mul(g2_generator<typename C::Fq>(), s, 8), out_g2_xy, out_g2_inf);
+    return VC_OK;
+}
+
+// a key of curve C: [s]_2 checked (not the identity, on the twist, of order r), its tables made
+template <class C>
+int vk_new(const uint64_t* g2_xy, uint8_t g2_inf, size_t size, vc_kzg_vk** out) {
+    using Fq = typename C::Fq;
+    G2AffT<Fq> s2;
+    if (g2_inf || !g2_load(g2_xy, false, s2) || !g2_on_twist(s2) || !g2_in_subgroup(s2)) return VC_E_INVALID;
+    KzgKey<C>* key = new (std::nothrow) KzgKey<C>();
+    if (!key) return VC_E_OOM;
+    key->size = size;
+    key->curve = C::CURVE;
+    key->omega = group_gen_t<typename C::Fr>(size, fr_generator<typename C::Fr>());
+    key->s2 = s2;
+    ate_line_table(s2, key->lines);
+    ate_line_table(g2_generator<Fq>(), key->lines + C::PC::ATE_LINES);
+    *out = key;
+    return VC_OK;
+}
+
+template <class C>
+int verify(const KzgKey<C>& key, const uint64_t* com_xy, uint8_t com_inf, const uint64_t* point_fr,
+           const uint64_t* proof_xy, uint8_t proof_inf, const uint64_t* y_fr, int* result) {
+    using Fq = typename C::Fq;
+    if ((!com_xy && !com_inf) || !point_fr || (!proof_xy && !proof_inf) || !y_fr || !result) return VC_E_INVALID;
+    *result = 0;
+    uint32_t y[8], pt[8], w[C::PW];
+    if (!fr_words<typename C::Fr>(y_fr, y) || !fr_words<typename C::Fr>(point_fr, pt)) return VC_OK;
+    SWAff<Fq> Cm{fe_zero<Fq>(), fe_zero<Fq>()}, pi = Cm;
+    if (!com_inf) {
+        memcpy(w, com_xy, sizeof w);
+        if (!g1_load(w, Cm)) return VC_OK;
+    }
+    if (!proof_inf) {
+        memcpy(w, proof_xy, sizeof w);
+        if (!g1_load(w, pi)) return VC_OK;
+    }
+    uint32_t p[8];
+    kzg_eval_point(key.omega, key.size, pt, p);
+    *result = kzg_check(Cm, com_inf != 0, pi, proof_inf != 0, y, p, key.lines, key.lines + C::PC::ATE_LINES) ? 1 : 0;
+    return VC_OK;
+}
+
+template <class C>
+int pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy, const uint8_t* g2_inf,
+                  int* result) {
+    using Fq = typename C::Fq;
+    if (!result || (n && (!g1_xy || !g1_inf || !g2_xy || !g2_inf)) || n > (size_t(1) << 20)) return VC_E_INVALID;
+    std::vector<G1EvalT<Fq>> P(n);
+    std::vector<G2AffT<Fq>> Q(n);
+    for (size_t i = 0; i < n; i++) {
+        SWAff<Fq> a{fe_zero<Fq>(), fe_zero<Fq>()};
+        if (!g1_inf[i]) {
+            uint32_t w[C::PW];
+            memcpy(w, g1_xy + C::PW / 2 * i, sizeof w);
+            if (!g1_load(w, a)) return VC_E_INVALID;
+        }
+        P[i] = g1_eval_aff(a.x, a.y, g1_inf[i] != 0);
+        if (!g2_load(g2_xy + C::PW * i, g2_inf[i] != 0, Q[i]) || !g2_on_twist(Q[i]) || !g2_in_subgroup(Q[i]))
+            return VC_E_INVALID;
+    }
+    *result = pairing_product_is_one((int)n, P.data(), Q.data()) ? 1 : 0;
+    return VC_OK;
+}
 
 }  // namespace
 
 int vk::kzg_vk_curve(const vc_kzg_vk* vk) { return vk->curve; }
 
-bool vk::kzg_pair_check(const vc_kzg_vk* vk, const G1A& P1, const G1A& P2) {
-    return kzgb::pair_check(P1, P2, vk->lines, vk->lines + PC::ATE_LINES);
-}
-
 extern "C" {
 
-int vc_kzg_g2_from_secret(const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf) {
-    uint32_t s[8];
-    if (!secret_fr || !out_g2_xy || !out_g2_inf || !fr_words(secret_fr, s)) return VC_E_INVALID;
-    g2_store(g2_mul(g2_generator(), s, 8), out_g2_xy, out_g2_inf);
-    return VC_OK;
+int vc_kzg_g2_from_secret_curve(int curve, const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf) {
+    if (curve == VC_CURVE_BN254) return g2_from_secret<BN254Kzg>(secret_fr, out_g2_xy, out_g2_inf);
+    if (curve == VC_CURVE_BLS12_381) return g2_from_secret<BLS381Kzg>(secret_fr, out_g2_xy, out_g2_inf);
+    return VC_E_INVALID;
 }
 
-int vc_kzg_g2_from_secret_curve(int curve, const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf) {
-    if (curve == VC_CURVE_BN254) return vc_kzg_g2_from_secret(secret_fr, out_g2_xy, out_g2_inf);
-    if (curve == VC_CURVE_BLS12_381) return blsk::g2_from_secret(secret_fr, out_g2_xy, out_g2_inf);
-    return VC_E_INVALID;
+int vc_kzg_g2_from_secret(const uint64_t* secret_fr, uint64_t* out_g2_xy, uint8_t* out_g2_inf) {
+    return vc_kzg_g2_from_secret_curve(VC_CURVE_BN254, secret_fr, out_g2_xy, out_g2_inf);
 }
 
 int vc_kzg_vk_new_curve(int curve, const uint64_t* g2_xy, uint8_t g2_inf, size_t size, vc_kzg_vk** out) {
     if (curve != VC_CURVE_BN254 && curve != VC_CURVE_BLS12_381) return VC_E_INVALID;
     if (!g2_xy || !out || size == 0 || (size & (size - 1)) || size > (size_t(1) << 28)) return VC_E_INVALID;
-    G2Aff s2{fq2_zero(), fq2_zero(), true};
-    vc_kzg_vk_bls* tables = nullptr;
-    if (curve == VC_CURVE_BN254) {
-        if (g2_inf || !g2_load(g2_xy, false, s2) || !g2_on_twist(s2) || !g2_in_subgroup(s2)) return VC_E_INVALID;
-    } else {
-        const int st = blsk::vk_tables_new(g2_xy, g2_inf, size, &tables);
-        if (st != VC_OK) return st;
-    }
-    vc_kzg_vk* vk = new (std::nothrow) vc_kzg_vk();
-    if (!vk) {
-        blsk::vk_tables_free(tables);
-        return VC_E_OOM;
-    }
+    vc_kzg_vk* key = nullptr;
+    const int st = curve == VC_CURVE_BN254 ? vk_new<BN254Kzg>(g2_xy, g2_inf, size, &key)
+                                           : vk_new<BLS381Kzg>(g2_xy, g2_inf, size, &key);
+    if (st != VC_OK) return st;
     static std::atomic<uint64_t> next_uid{1};  // one sequence for both curves: the contexts' cache key
-    vk->uid = next_uid.fetch_add(1);
-    vk->size = size;
-    vk->curve = curve;
-    vk->bls = tables;
-    if (curve == VC_CURVE_BN254) {
-        vk->omega = bn254_group_gen(size);
-        vk->s2 = s2;
-        ate_line_table(s2, vk->lines);
-        ate_line_table(g2_generator(), vk->lines + PC::ATE_LINES);
-    }
-    *out = vk;
+    key->uid = next_uid.fetch_add(1);
+    *out = key;
     return VC_OK;
 }
 
@@ -103,56 +153,28 @@ int vc_kzg_vk_new(const uint64_t* g2_xy, uint8_t g2_inf, size_t size, vc_kzg_vk*
     return vc_kzg_vk_new_curve(VC_CURVE_BN254, g2_xy, g2_inf, size, out);
 }
 
-void vc_kzg_vk_free(vc_kzg_vk* vk) {
-    if (vk) blsk::vk_tables_free(vk->bls);
-    delete vk;
+void vc_kzg_vk_free(vc_kzg_vk* vk) {  // as what it was allocated as
+    if (!vk) return;
+    if (vk->curve == VC_CURVE_BLS12_381) delete static_cast<KzgKey<BLS381Kzg>*>(vk);
+    else delete static_cast<KzgKey<BN254Kzg>*>(vk);
 }
 
 int vc_kzg_verify(const vc_kzg_vk* vk, const uint64_t* com_xy, uint8_t com_inf, const uint64_t* point_fr,
                   const uint64_t* proof_xy, uint8_t proof_inf, const uint64_t* y_fr, int* result) {
-    if (is_bls(vk)) return blsk::verify(vk, com_xy, com_inf, point_fr, proof_xy, proof_inf, y_fr, result);
-    if (!vk || (!com_xy && !com_inf) || !point_fr || (!proof_xy && !proof_inf) || !y_fr || !result) return VC_E_INVALID;
-    *result = 0;
-    uint32_t y[8], pt[8], w[16];
-    if (!fr_words(y_fr, y) || !fr_words(point_fr, pt)) return VC_OK;
-    G1P C{fe_zero<BN254Fq>(), fe_zero<BN254Fq>()}, pi = C;
-    if (!com_inf) {
-        memcpy(w, com_xy, 64);
-        if (!g1_load(w, C)) return VC_OK;
-    }
-    if (!proof_inf) {
-        memcpy(w, proof_xy, 64);
-        if (!g1_load(w, pi)) return VC_OK;
-    }
-    uint32_t p[8];
-    kzg_eval_point(vk->omega, vk->size, pt, p);
-    *result = kzg_check(C, com_inf != 0, pi, proof_inf != 0, y, p, vk->lines, vk->lines + PC::ATE_LINES) ? 1 : 0;
-    return VC_OK;
+    if (!vk) return VC_E_INVALID;
+    if (vk->curve == VC_CURVE_BLS12_381)
+        return verify(kzg_key<BLS381Kzg>(vk), com_xy, com_inf, point_fr, proof_xy, proof_inf, y_fr, result);
+    return verify(kzg_key<BN254Kzg>(vk), com_xy, com_inf, point_fr, proof_xy, proof_inf, y_fr, result);
 }
 
 int vc_bn254_pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
                            const uint8_t* g2_inf, int* result) {
-    if (!result || (n && (!g1_xy || !g1_inf || !g2_xy || !g2_inf)) || n > (size_t(1) << 20)) return VC_E_INVALID;
-    std::vector<G1Eval> P(n);
-    std::vector<G2Aff> Q(n);
-    for (size_t i = 0; i < n; i++) {
-        G1P a{fe_zero<BN254Fq>(), fe_zero<BN254Fq>()};
-        if (!g1_inf[i]) {
-            uint32_t w[16];
-            memcpy(w, g1_xy + 8 * i, 64);
-            if (!g1_load(w, a)) return VC_E_INVALID;
-        }
-        P[i] = g1_eval_aff(a.x, a.y, g1_inf[i] != 0);
-        if (!g2_load(g2_xy + 16 * i, g2_inf[i] != 0, Q[i]) || !g2_on_twist(Q[i]) || !g2_in_subgroup(Q[i]))
-            return VC_E_INVALID;
-    }
-    *result = pairing_product_is_one((int)n, P.data(), Q.data()) ? 1 : 0;
-    return VC_OK;
+    return pairing_check<BN254Kzg>(n, g1_xy, g1_inf, g2_xy, g2_inf, result);
 }
 
 int vc_bls12_381_pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
                                const uint8_t* g2_inf, int* result) {
-    return blsk::pairing_check(n, g1_xy, g1_inf, g2_xy, g2_inf, result);
+    return pairing_check<BLS381Kzg>(n, g1_xy, g1_inf, g2_xy, g2_inf, result);
 }
 
 }  // extern "C"

@@ -1,31 +1,33 @@
-// The KZG verifying key shared by the host verifier (pairing_host.cpp) and the batched device
-// verifier (pairing.hip). A BLS12-381 key keeps its own tables (pairing_bls_internal.hpp) behind
-// `bls`; the BN254 members are then unused.
+// The KZG verifying key shared by the host verifier (pairing_host.cpp), the batched device
+// verifier (pairing.hip) and the batch fold (kzg_batch.hip): what every key has, and behind it the
+// tables of the key's own curve (vk::KzgKey<C>, C a curve of kzg_curves.hpp). The C ABI hands out
+// vc_kzg_vk*; an entry point looks at `curve` and goes on with kzg_key<C>.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
-#include "host/fr.hpp"
 #include "pairing.hpp"
-
-struct vc_kzg_vk_bls;
+#include "pairing_bls.hpp"
 
 struct vc_kzg_vk {
-    uint64_t uid = 0;  // unique per key ever made (a freed key's address can come back): the
-                       // contexts key their uploaded copies of the tables on it
+    uint64_t uid = 0;  // unique per key ever made, one sequence for all curves (a freed key's address
+                       // can come back): the contexts key their uploaded copies of the tables on it
     size_t size = 0;   // the domain
-    vk::Fr omega;      // its generator (Montgomery)
-    vk::bn::G2Aff s2;  // [s]_2
-    // Miller-loop lines of [s]_2, then of H
-    vk::bn::LineCoef lines[2 * vk::bn::PC::ATE_LINES];
-    int curve = 0;                 // VC_CURVE_BN254 or VC_CURVE_BLS12_381
-    vc_kzg_vk_bls* bls = nullptr;  // the BLS12-381 key's tables (owned; vc_kzg_vk_free)
+    int curve = 0;     // VC_CURVE_BN254 or VC_CURVE_BLS12_381
 };
 
 namespace vk {
-// e(P1, [s]_2) e(P2, H) == 1 over the key's tables for two points of G1 as accumulators, the
-// identity included (pairing_host.cpp; the batch verifier's final check: vc_kzg_verify's inputs
-// cannot express it)
-bool kzg_pair_check(const vc_kzg_vk* vk, const bn::G1A& P1, const bn::G1A& P2);
+template <class C>
+struct KzgKey : vc_kzg_vk {
+    fe<typename C::Fr> omega;         // the domain's generator (Montgomery)
+    ate::G2AffT<typename C::Fq> s2;  // [s]_2
+    // Miller-loop lines of [s]_2, then of H
+    ate::LineCoefT<typename C::Fq> lines[2 * C::PC::ATE_LINES];
+};
+// a key of curve C::CURVE as what it was allocated as
+template <class C>
+inline const KzgKey<C>& kzg_key(const vc_kzg_vk* vk) {
+    return *static_cast<const KzgKey<C>*>(vk);
+}
 int kzg_vk_curve(const vc_kzg_vk* vk);
 }  // namespace vk

@@ -65,12 +65,6 @@ void expand_message_xmd(const uint8_t* msg, size_t n, const uint8_t* dst, size_t
     expand_message_xmd_feed([&](Sha256& h) { h.update(msg, n); }, dst, dlen, out_len, out);
 }
 
-Fr hash_to_fr(const uint8_t* msg, size_t n, const uint8_t* dst, size_t dlen) {
-    uint8_t u[kLenPerElem];
-    expand_message_xmd(msg, n, dst, dlen, kLenPerElem, u);
-    return fe_from_be_bytes_mod<BN254Fr>(u, kLenPerElem);
-}
-
 // ---------------------------------------------------------------- compressed encoding
 // SWFlags: byte[31] |= 0x80 if y > -y (YIsNegative), 0x40 for infinity (x = 0)
 void compress_g1(const uint64_t* xy, bool inf, uint8_t out[32]) {

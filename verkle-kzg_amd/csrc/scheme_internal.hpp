@@ -12,7 +12,15 @@ namespace vk {
 Fr transcript_digest(vc_transcript* t, const char* label);
 void transcript_append_point(vc_transcript* t, const uint64_t* xy, bool inf, const char* label);
 void transcript_append_fr(vc_transcript* t, const Fr& mont, const char* label);
-Fr hash_to_fr(const uint8_t* msg, size_t n, const uint8_t* dst, size_t dlen);
+void expand_message_xmd(const uint8_t* msg, size_t n, const uint8_t* dst, size_t dlen, size_t out_len, uint8_t* out);
+// ark-ff 0.4 DefaultFieldHasher<Sha256, 128> into the scalar field F: ceil((bits + 128) / 8) = 48
+// bytes for a 254- or a 255-bit modulus, read big-endian and reduced mod r (Montgomery out)
+template <class F = BN254Fr>
+inline fe<F> hash_to_fr(const uint8_t* msg, size_t n, const uint8_t* dst, size_t dlen) {
+    uint8_t u[48];
+    expand_message_xmd(msg, n, dst, dlen, sizeof u, u);
+    return fe_from_be_bytes_mod<F>(u, sizeof u);
+}
 void compress_g1(const uint64_t* xy, bool inf, uint8_t out[32]);
 // grow the transcript state by n bytes and return the start of the new region (callers that
 // serialise many records on several threads)
