@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY (never shipped, never measured).
 
 Restatement of the engine's signed-window scalar decomposition
-(verkle-kzg_amd/csrc/msm.hip: choose_window, for_each_digit, k_glv_split, msm_run_t's window
+(verkle-kzg_amd/csrc/: msm_plan.hpp choose_window, msm_digits.hpp for_each_digit and k_glv_split, msm.hip msm_run_t's window
 slices), used to check the window-sliced multi-GPU split (vc_msm_device_window_part): the
 part-k MSM equals sum_i s_i^(k) P_i with s_i^(k) = sum_{w in [kW/G, (k+1)W/G)} d_iw 2^(c w)
 (with the GLV split on BLS12-381: the digits of both halves, the k2 half weighted by lambda),
@@ -34,13 +34,13 @@ def glv_split(k, r):
 
 
 def top_shortfall(c, total):
-    """bits the top window of `total` digit bits in c-bit windows lacks (msm.hip top_shortfall)"""
+    """bits the top window of `total` digit bits in c-bit windows lacks (msm_plan.hpp top_shortfall)"""
     W = (total + c - 1) // c
     return c - (total - c * (W - 1))
 
 
 def choose_window(n, total):
-    """msm.hip choose_window: the size rule, unless its top window is short by more than 2 bits;
+    """msm_plan.hpp choose_window: the size rule, unless its top window is short by more than 2 bits;
     then the cheapest c in c0 - 5 .. c0 + 2 (W n + 2 W 2^(c-1)) whose top window is not."""
     c0 = 5
     for lim, c in ((1 << 19, 16), (1 << 17, 15), (1 << 15, 13), (1 << 12, 11), (1 << 9, 9), (64, 7)):
@@ -112,7 +112,7 @@ def part_scalars(curve, scalars, part, parts, r):
     return out
 
 
-# Radix-B shared windows (msm.hip k_glv_radix / radix_digits, the one-GPU whole-table GLV MSM):
+# Radix-B shared windows (msm_digits.hpp k_glv_radix / radix_digits, the one-GPU whole-table GLV MSM):
 # B = 5 * 2^16, 7 windows (B^7 / 2 > 2^127), B / 2 = 5 * 2^15 buckets in one set.
 RADIX_MUL, RADIX_C0, RADIX_W = 5, 16, 7
 
@@ -168,7 +168,7 @@ def radix_bucket_sum_residue(buckets, lseg):
 
 def bit_sums_marginal(R, h):
     """T_j = sum_{s: bit j of s} R_s by the marginal form of msm_tail.hip k_msm_bitsum /
-    PartLoc (msm_tail.hpp msm_tail_plan): with s = G hi + lo (G = 2^h), the column sums
+    PartLoc (msm_plan.hpp msm_tail_plan): with s = G hi + lo (G = 2^h), the column sums
     L_lo = sum_hi R_{G hi + lo} and row sums H_hi = sum_lo R_{G hi + lo}; T_j is the sum of the
     L_lo with bit j of lo (j < h) or of the H_hi with bit j - h of hi (j >= h)."""
     S = len(R)
@@ -182,7 +182,7 @@ def bit_sums_marginal(R, h):
 
 
 def bit_sums_marginal_urow(R, h, pL):
-    """The row-derived total of the marginal form (msm_tail.hpp TailPlan::urow, msm_tail.hip
+    """The row-derived total of the marginal form (msm_plan.hpp TailPlan::urow, msm_tail.hip
     PartLoc, msm.hip slice_finish), for Lseg = 1 where the total U = sum_s R_s is wanted beside the
     T_j: every column sum L_lo is made as pL partials (pL waves over Hn / pL rows each); T_j (j < h)
     sums the partials of the columns with bit j of lo, T_j (j >= h) the row sums H_hi with bit j - h

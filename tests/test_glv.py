@@ -1,7 +1,7 @@
-"""CPU checks of the GLV split the engine applies to BLS12-381 MSMs (verkle-kzg_amd/csrc/msm.hip:
-k_glv_split, k_glv_phi, k_glv_check), through its oracle restatement (oracle/pyoracle/pippenger.py):
-the halves recombine to k mod r, stay below 2^127 at every edge of the balancing, the window
-slices of the split add up to the whole scalar, and the curve constants do what msm.hip assumes
+"""CPU checks of the GLV split the engine applies to BLS12-381 MSMs (verkle-kzg_amd/csrc/:
+msm_digits.hpp k_glv_split, msm_tables.hip k_glv_phi, k_glv_check), through its oracle restatement
+(oracle/pyoracle/pippenger.py): the halves recombine to k mod r, stay below 2^127 at every edge of the
+balancing, the window slices of the split add up to the whole scalar, and the curve constants do what the MSM assumes
 (phi = [lambda] on the subgroup; the subgroup test rejects points outside it)."""
 import random
 
@@ -85,7 +85,7 @@ def test_glv_curve_constants():
 
 
 def test_radix_digits_recombine_and_bound():
-    """k_glv_radix / radix_digits (msm.hip): the GLV halves in radix B = 5 * 2^16, 7 signed digits
+    """k_glv_radix / radix_digits (msm_digits.hpp): the GLV halves in radix B = 5 * 2^16, 7 signed digits
     |d_w| <= B/2 (bucket |d| - 1 < 5 * 2^15), the top digit never negative and never carrying."""
     from pyoracle import pippenger
     from pyoracle.curves import BLS12_381 as C

@@ -1,4 +1,4 @@
-"""GPU parity: the HIP Pippenger MSM (vc_msm) against the C restatement of the reference
+"""GPU parity: the HIP Pippenger MSM (vc_msm; csrc/msm.hip and the files it includes) against the C restatement of the reference
 MSM (oracle/c/ref_curve.c = utils::inner_product, utils.rs:16-19), bit-exact on canonical
 affine coordinates, for BN254 G1 (the reference's curve), BLS12-381 G1 and Bandersnatch."""
 import random
@@ -372,7 +372,7 @@ def test_batch_commit_sparse(engines, oracle_c, curve):
 
 @pytest.mark.parametrize("nnz_mod", [0, 1, 255])
 def test_batch_commit_sparse_fused_equals_launches(engines, oracle_c, nnz_mod, monkeypatch):
-    """The sparse commit's fused count + scan and expand + row offsets (msm.hip
+    """The sparse commit's fused count + scan and expand + row offsets (sparse_commit.hip
     k_sparse_count_scan / k_sparse_expand_rows: one block per 256 non-zeros, the last block scans
     the block totals) == the separate launches (VKZG_SPARSE_FUSED=0: count, hipcub scan, expand,
     row offsets), bit for bit, on ~40,000 BN254 rows of 0-4 non-zeros whose count is 256 k + nnz_mod

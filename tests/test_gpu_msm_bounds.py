@@ -1,5 +1,5 @@
 """GPU parity of the accumulate's bucket bounds: the thread-start records the fine sort writes
-(msm.hip AccStart), the next bucket's end loaded one bucket ahead inside the loop, the entry
+(msm_accumulate.hpp AccStart, msm_sort.hpp k_sort_fine), the next bucket's end loaded one bucket ahead inside the loop, the entry
 index loaded two entries ahead and the chain lengths taken from the records -- against the C
 oracle's group law, bit-exact, as tests/test_gpu_msm.py does.
 

@@ -1078,7 +1078,7 @@ int normalize_rows_items(vc_ctx* ctx, void* d_rows, size_t n, const uint32_t* ad
     // (per-kernel timing keeps the late launch: the finish's events would count the host's wait)
     NormGo go;
     const bool early_now = early && !ctx->timing;
-    DevBuf& cnt = ctx->ws[WS_NORM_CNT];  // word 0: the prep's arrival counter; word 16: the sparse commits' (msm.hip k_sparse_count_scan); bytes [128, 200): the relay
+    DevBuf& cnt = ctx->ws[WS_NORM_CNT];  // word 0: the prep's arrival counter; word 16: the sparse commits' (sparse_commit.hip k_sparse_count_scan); bytes [128, 200): the relay
     if (cnt.p == nullptr) {
         VK_TRY(cnt.ensure(256));
         VK_CHECK_HIP(hipMemsetAsync(cnt.p, 0, 256, ctx->stream));

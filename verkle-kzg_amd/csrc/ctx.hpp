@@ -197,7 +197,7 @@ enum WsSlot {
     WS_SP_ITEMS,  // to_data_item of the sparse commits' rows (msm_batch_sparse_items)
     WS_NORM_CNT,  // the verkle normalisation's arrival counter (zero between launches)
     WS_NORM_TOT,  // its block products and per-block cofactors (device scan)
-    WS_STARTS,    // the accumulate threads' start records (msm.hip AccStart), written by k_sort_fine
+    WS_STARTS,    // the accumulate threads' start records (msm_accumulate.hpp AccStart), written by k_sort_fine
     WS_COUNT_
 };
 
@@ -397,7 +397,7 @@ int msm_batch_sparse_items_guarded(vc_ctx* ctx, int table, size_t batch, const u
 // structure row_ptr on the host (rows_fit: every row has 1..4 non-zeros -- the chunks are the rows);
 // affine rows, flags and items written to device memory, enqueued on ctx->stream (verkle.cpp's
 // device-resident levels)
-// the sparse commits' latency path (msm.hip k_fb_sparse_small, BN254): rows of (column, scalar)
+// the sparse commits' latency path (sparse_commit.hip k_fb_sparse_small, BN254): rows of (column, scalar)
 // non-zeros; mode 0: d_vals (4 canonical words per non-zero), 1: d_vals of 2 words (16-byte
 // values), 2: d_item[d_child[j]] - (d_sidx && d_sidx[j] >= 0 ? d_snap[d_sidx[j]] : 0). Row g
 // also adds the point (d_add_xy, d_add_inf)[d_add_ids[g]] if given (0xffffffff: none); its

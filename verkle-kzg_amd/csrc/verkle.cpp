@@ -1267,7 +1267,7 @@ int verkle_commitment_dev(vc_ctx* ctx, int table, vc_verkle* t, uint64_t* out_xy
         return VC_OK;
     };
     // levels of at most this many (non-zero, window) pairs take the sparse commits' latency path
-    // (a wave per 64 pairs, msm.hip k_fb_sparse_small) instead of the sort-based one: an update's
+    // (a wave per 64 pairs, sparse_commit.hip k_fb_sparse_small) instead of the sort-based one: an update's
     // levels; VKZG_SPARSE_SMALL_MAX (pairs, read per call; 0 = never) is the A/B knob
     const char* small_env = getenv("VKZG_SPARSE_SMALL_MAX");
     const size_t small_max = small_env ? (size_t)atoll(small_env) : (size_t)1 << 18;

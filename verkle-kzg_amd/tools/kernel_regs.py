@@ -1,7 +1,8 @@
 """Register use of the kernels in the built libvkzg.so (no GPU needed): unbundles the gfx950 code
 object from the .hip_fatbin section and reads each kernel's AMDGPU metadata note (llvm-readelf).
 usage: kernel_regs.py [lib] [name-substring]  -> "name vgpr_count agpr_count spills" lines.
-Used by tests/test_abi.py to pin the occupancy of the hot kernels (k_msm_accumulate must stay at
+Used by tests/test_abi.py to pin the occupancy of the hot kernels (k_msm_accumulate, csrc/msm_accumulate.hpp,
+instantiated by msm.hip and sparse_commit.hip, must stay at
 <= 256 VGPRs + AGPRs: two waves per SIMD; a variant at 268 ran at one wave and 15 % slower)."""
 import os
 import re
