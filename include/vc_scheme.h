@@ -190,6 +190,44 @@ int vc_kzg_prove_many(vc_ctx* ctx, int table, size_t N, size_t rows, size_t widt
 int vc_kzg_prove_many_device(vc_ctx* ctx, int table, size_t N, size_t rows, size_t width, const void* d_data,
                              const uint32_t* row, const uint64_t* points, size_t n, uint64_t* proof_xy,
                              uint8_t* proof_inf, uint64_t* y);
+/* Subvector proofs: one constant-size proof that k positions of one committed row hold k values --
+ * what the reference's prove_batch / verify_batch name (kzg/mod.rs:156-163, 191-197) and leave
+ * todo!(). Domain of size N with generator w, row f (zero beyond `width`), S a set of k distinct
+ * indices below N, Z_S(X) = prod_{i in S} (X - w^i), I the polynomial of degree < k with
+ * I(w^i) = f_i on S. The proof is pi_S = [q(s)]_1 with q = (f - I) / Z_S, the values are y_i = f_i
+ * in the caller's index order, and the verifier accepts when
+ *   e(pi_S, [Z_S(s)]_2) == e(C - [I(s)]_1, H).
+ * With c_i = 1 / Z_S'(w^i) = prod_{l in S, l != i} 1 / (w^i - w^l): q = sum_{i in S} c_i q^(i), q^(i)
+ * the single-point quotient of index i, hence pi_S = sum_i c_i pi_i over vc_kzg_prove's proofs.
+ * k = 1 is vc_kzg_prove at that index; k = N gives the identity.
+ *
+ * n subsets in one call: subset s is idx[idx_off[s] .. idx_off[s + 1]) (1 <= k_s <= N) and proves
+ * row row[s] (row == NULL: row s, and then rows == n) of `data`, as vc_kzg_prove_many's rows. The
+ * proof does not depend on the order of a subset's indices; y[p] is the value at idx[p]. Per chunk
+ * of at most 16,384 subsets: one field launch, a wave per subset, and one batched fixed-base commit.
+ * BN254 and BLS12-381, 2 <= N <= 1024.
+ * A status other than VC_OK is decided on the host before any GPU work and leaves the outputs
+ * untouched: VC_E_INVALID (an index >= N, a repeated index inside one subset, an empty subset, a
+ * non-monotone idx_off, or any of vc_kzg_prove_many's argument rules), VC_E_RANGE, VC_E_TABLE as
+ * there. n == 0 is VC_OK.
+ * idx_off: n + 1 u32; idx: idx_off[n] u32; proof_xy: n x 2 NL u64; proof_inf: n; y: idx_off[n] x 4 u64. */
+int vc_kzg_prove_subvector_many(vc_ctx* ctx, int table, size_t N, size_t rows, size_t width, const uint64_t* data,
+                                const uint32_t* row, const uint32_t* idx_off, const uint32_t* idx, size_t n,
+                                uint64_t* proof_xy, uint8_t* proof_inf, uint64_t* y);
+/* same with the rows already in device memory (rows x width canonical values, 4 u64 each) */
+int vc_kzg_prove_subvector_many_device(vc_ctx* ctx, int table, size_t N, size_t rows, size_t width,
+                                       const void* d_data, const uint32_t* row, const uint32_t* idx_off,
+                                       const uint32_t* idx, size_t n, uint64_t* proof_xy, uint8_t* proof_inf,
+                                       uint64_t* y);
+/* the k canonical weights c_i of the set idx[0 .. k) in the domain of size N (host, no context;
+ * curve: VC_CURVE_BN254 or VC_CURVE_BLS12_381), for an aggregator that holds single proofs already
+ * (vc_kzg_prove_all_points mode 1, vc_kzg_prove_many) and forms sum c_i pi_i with the MSM calls.
+ * VC_E_INVALID: N not a power of two in [2, 2^28], k == 0, an index >= N, a repeated index. */
+int vc_kzg_subvector_weights(int curve, size_t N, const uint32_t* idx, size_t k, uint64_t* c_out);
+/* [s^t]_1 for t < K from the Lagrange SRS alone (no secret): K batched commits of the rows
+ * (w^(j t))_j. out: K x 2 NL u64. 2 <= N <= 1024; VC_E_RANGE for K > N or a table with fewer than
+ * N points; VC_E_INVALID for K == 0 or when a power is the identity (s = 0 is no setup). */
+int vc_kzg_g1_powers(vc_ctx* ctx, int table, size_t N, size_t K, uint64_t* out);
 /* commit + prove_point in one call (configs[3]'s unit): C = commit(evals) (kzg/mod.rs:126-134) and
  * the proof at `point` as vc_kzg_prove_device; both MSMs over the SRS run as one batched
  * pipeline (vc_msm_device_many). */
@@ -383,6 +421,32 @@ int vc_kzg_batch_challenge_curve(int curve, const uint8_t seed[32], uint64_t* rh
  * also for a G1 input outside the subgroup */
 int vc_bls12_381_pairing_check(size_t n, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
                                const uint8_t* g2_inf, int* result);
+
+/* ---------------------------------------------------------------- KZG subvector verification
+ * The verifier of vc_kzg_prove_subvector_many's proofs (the statement is there). Host code on both
+ * curves, no context, no GPU. Its key holds powers of s: [s^t]_1 for t < K and [s^t]_2 for t <= K,
+ * in the curve's G1 / G2 layouts without identity flags, and verifies sets of up to K indices. */
+typedef struct vc_kzg_svk vc_kzg_svk;
+/* the powers from the secret, the counterpart of vc_kzg_g2_from_secret for tests and trusted setups
+ * (g1_out: K x 2 NL u64, g2_out: (K + 1) x 4 NL u64). VC_E_INVALID for K == 0, a secret >= r or 0. */
+int vc_kzg_powers_from_secret(int curve, const uint64_t* secret_fr, size_t K, uint64_t* g1_out, uint64_t* g2_out);
+/* The key of a domain of `size` (a power of two in [2, 2^28]), 1 <= K <= size. Every point is checked:
+ * coordinates below p, on its curve, G2 in the subgroup of order r (on BLS12-381 G1 too),
+ * g1[0] = G and g2[0] = H; anything else is VC_E_INVALID. That the powers belong to one s is NOT
+ * checked (it would take a pairing per power): the key is trusted input, as an SRS is. */
+int vc_kzg_svk_new(int curve, size_t size, size_t K, const uint64_t* g1_powers, const uint64_t* g2_powers,
+                   vc_kzg_svk** svk);
+void vc_kzg_svk_free(vc_kzg_svk* svk);
+/* One subvector proof: *result = 1 when e(pi, [Z_S(s)]_2) == e(C - [I(s)]_1, H), else 0. idx: k
+ * indices, y: k x 4 u64 in the indices' order (any order, the y permuted with the indices).
+ * The monomial coefficients of Z_S and of I = sum y_i c_i Z_S / (X - w^i) cost O(k^2) field
+ * multiplies; [Z_S(s)]_2 and [I(s)]_1 are joint double-and-adds over the key's powers.
+ * VC_E_RANGE for k > K; VC_E_INVALID for a bad index set (k == 0, an index >= size, a repeated
+ * index: the verifier's own input) or a null argument. Malformed proof content -- a coordinate >= p,
+ * a point off the curve, a y >= r, on BLS12-381 a G1 point outside the subgroup -- gives *result = 0
+ * with VC_OK, as vc_kzg_verify_many. The identity flag is a valid C and a valid proof. */
+int vc_kzg_verify_subvector(const vc_kzg_svk* svk, const uint64_t* com_xy, uint8_t com_inf, const uint32_t* idx,
+                            size_t k, const uint64_t* y, const uint64_t* proof_xy, uint8_t proof_inf, int* result);
 
 #ifdef __cplusplus
 }

@@ -17,32 +17,6 @@ using namespace vk::ate;
 
 namespace {
 
-// G2 in the ABI layout (x.c0 x.c1 y.c0 y.c1, canonical) -> Montgomery; false for a coordinate >= p
-template <class F>
-bool g2_load(const uint64_t* xy, bool inf, G2AffT<F>& out) {
-    constexpr int NW = F::N / 2;  // u64 words of a coordinate
-    out = G2AffT<F>{fq2_zero<F>(), fq2_zero<F>(), inf};
-    if (inf) return true;
-    fe<F>* dst[4] = {&out.x.c0, &out.x.c1, &out.y.c0, &out.y.c1};
-    for (int k = 0; k < 4; k++) {
-        uint32_t w[F::N];
-        memcpy(w, xy + NW * k, sizeof w);
-        if (!words_below_modulus<F>(w)) return false;
-        *dst[k] = canon_to_mont<F>(xy + NW * k);
-    }
-    return true;
-}
-template <class F>
-void g2_store(const G2AffT<F>& p, uint64_t* xy, uint8_t* inf) {
-    constexpr int NW = F::N / 2;
-    memset(xy, 0, 8 * 4 * NW);
-    *inf = p.inf ? 1 : 0;
-    if (p.inf) return;
-    mont_to_canon<F>(p.x.c0, xy);
-    mont_to_canon<F>(p.x.c1, xy + NW);
-    mont_to_canon<F>(p.y.c0, xy + 2 * NW);
-    mont_to_canon<F>(p.y.c1, xy + 3 * NW);
-}
 template <class Fr>
 bool fr_words(const uint64_t* fr, uint32_t* w) {  // canonical words; false when >= r
     memcpy(w, fr, 32);

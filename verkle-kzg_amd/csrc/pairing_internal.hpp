@@ -6,6 +6,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string.h>
+
+#include "host/fr.hpp"
 #include "pairing.hpp"
 #include "pairing_bls.hpp"
 
@@ -30,4 +33,32 @@ inline const KzgKey<C>& kzg_key(const vc_kzg_vk* vk) {
     return *static_cast<const KzgKey<C>*>(vk);
 }
 int kzg_vk_curve(const vc_kzg_vk* vk);
+
+// G2 in the ABI layout (x.c0 x.c1 y.c0 y.c1, canonical) -> Montgomery; false for a coordinate >= p
+// (the host entry points: pairing_host.cpp, kzg_sub_host.cpp)
+template <class F>
+inline bool g2_load(const uint64_t* xy, bool inf, ate::G2AffT<F>& out) {
+    constexpr int NW = F::N / 2;  // u64 words of a coordinate
+    out = ate::G2AffT<F>{ate::fq2_zero<F>(), ate::fq2_zero<F>(), inf};
+    if (inf) return true;
+    fe<F>* dst[4] = {&out.x.c0, &out.x.c1, &out.y.c0, &out.y.c1};
+    for (int k = 0; k < 4; k++) {
+        uint32_t w[F::N];
+        memcpy(w, xy + NW * k, sizeof w);
+        if (!ate::words_below_modulus<F>(w)) return false;
+        *dst[k] = canon_to_mont<F>(xy + NW * k);
+    }
+    return true;
+}
+template <class F>
+inline void g2_store(const ate::G2AffT<F>& p, uint64_t* xy, uint8_t* inf) {
+    constexpr int NW = F::N / 2;
+    memset(xy, 0, 8 * 4 * NW);
+    *inf = p.inf ? 1 : 0;
+    if (p.inf) return;
+    mont_to_canon<F>(p.x.c0, xy);
+    mont_to_canon<F>(p.x.c1, xy + NW);
+    mont_to_canon<F>(p.y.c0, xy + 2 * NW);
+    mont_to_canon<F>(p.y.c1, xy + 3 * NW);
+}
 }  // namespace vk

@@ -101,6 +101,17 @@ SIGNATURES = {
     "vc_kzg_prove": (c_int, [c_void_p, c_int, c_size_t, P, c_size_t, P, P, P, P]),
     "vc_kzg_prove_many": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_size_t, P, P, P, c_size_t, P, P, P]),
     "vc_kzg_prove_many_device": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_size_t, P, P, P, c_size_t, P, P, P]),
+    "vc_kzg_prove_subvector_many": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_size_t, P, P, P, P, c_size_t, P, P,
+                                            P]),
+    "vc_kzg_prove_subvector_many_device": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_size_t, P, P, P, P, c_size_t,
+                                                   P, P, P]),
+    "vc_kzg_subvector_weights": (c_int, [c_int, c_size_t, P, c_size_t, P]),
+    "vc_kzg_g1_powers": (c_int, [c_void_p, c_int, c_size_t, c_size_t, P]),
+    "vc_kzg_powers_from_secret": (c_int, [c_int, P, c_size_t, P, P]),
+    "vc_kzg_svk_new": (c_int, [c_int, c_size_t, c_size_t, P, P, ctypes.POINTER(c_void_p)]),
+    "vc_kzg_svk_free": (None, [c_void_p]),
+    "vc_kzg_verify_subvector": (c_int, [c_void_p, P, ctypes.c_uint8, P, c_size_t, P, P, ctypes.c_uint8,
+                                        ctypes.POINTER(c_int)]),
     "vc_kzg_quotient": (c_int, [c_void_p, c_size_t, P, c_size_t, P, P, P]),
     "vc_kzg_prove_all_points": (c_int, [c_void_p, c_int, c_size_t, P, c_size_t, c_int, P, P, P,
                                         ctypes.POINTER(c_size_t)]),

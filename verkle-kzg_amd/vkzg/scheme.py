@@ -3,7 +3,8 @@
 Mirrors /root/reference/vector-commit/src: `IPA` (ipa/mod.rs), `KZG` (kzg/mod.rs),
 `LagrangeBasis` (lagrange_basis.rs), `TranscriptHasher` (transcript.rs),
 `prove_multiproof` / `verify_multiproof` / `verify_multiproof_kzg` (multiproof.rs), `to_data_item`
-(lib.rs:56-67). KZG openings are verified with pairings through `KZGVerifyingKey`.
+(lib.rs:56-67). KZG openings are verified with pairings through `KZGVerifyingKey`; subvector proofs
+(`KZG.prove_subvector`, the reference's prove_batch) through `KZGSubvectorKey`.
 Same names, argument meaning and error behaviour (errors raise `VCError` where the Rust
 returns Err or panics). Curve: BN254 G1 (the reference's only instantiation); `KZG`,
 `KZGVerifyingKey`, `kzg_g2_from_secret`, `kzg_batch_challenge` and `pairing_check` also work on
@@ -438,16 +439,19 @@ def _g2_array(Q, nl=4):
     return xy, 0
 
 
+def _g2_tuple(xy, nl):
+    """the ABI's G2 layout -> ((x.c0, x.c1), (y.c0, y.c1))"""
+    v = [limbs_to_int(xy[nl * k:nl * k + nl]) for k in range(4)]
+    return ((v[0], v[1]), (v[2], v[3]))
+
+
 def kzg_g2_from_secret(secret, curve="bn254"):
     """[secret]_2 = secret * H (kzg/mod.rs:122) as ((x.c0, x.c1), (y.c0, y.c1)), None = identity."""
     r, nl, cid = _curve_params(curve)
     xy = np.zeros(4 * nl, dtype=np.uint64)
     inf = np.zeros(1, dtype=np.uint8)
     check(lib().vc_kzg_g2_from_secret_curve(cid, _p(_fr(secret, r)), _p(xy), _p(inf)), "kzg_g2_from_secret")
-    if inf[0]:
-        return None
-    v = [limbs_to_int(xy[nl * k:nl * k + nl]) for k in range(4)]
-    return ((v[0], v[1]), (v[2], v[3]))
+    return None if inf[0] else _g2_tuple(xy, nl)
 
 
 def pairing_check(pairs, curve="bn254"):
@@ -568,6 +572,65 @@ def kzg_batch_challenge(seed, curve="bn254"):
     return limbs_to_int(out)
 
 
+def kzg_subvector_weights(size, indexes, curve="bn254"):
+    """The weights c_i = 1 / Z_S'(w^i) of a subvector proof over the index set (vc_kzg_subvector_weights):
+    pi_S = sum c_i pi_i over the single openings' proofs. Host code."""
+    _, _, cid = _curve_params(curve)
+    idx = np.ascontiguousarray(np.asarray(indexes, dtype=np.uint32))
+    out = np.zeros((max(len(idx), 1), 4), dtype=np.uint64)
+    check(lib().vc_kzg_subvector_weights(cid, size, _p(idx), len(idx), _p(out)), "kzg_subvector_weights")
+    return [limbs_to_int(out[i]) for i in range(len(idx))]
+
+
+def kzg_powers_from_secret(secret, K, curve="bn254"):
+    """([s^t]_1 for t < K, [s^t]_2 for t <= K) from the secret (vc_kzg_powers_from_secret): tests and
+    trusted setups. Host code."""
+    r, nl, cid = _curve_params(curve)
+    g1 = np.zeros((K, 2 * nl), dtype=np.uint64)
+    g2 = np.zeros((K + 1, 4 * nl), dtype=np.uint64)
+    check(lib().vc_kzg_powers_from_secret(cid, _p(_fr(secret, r)), K, _p(g1), _p(g2)), "kzg_powers_from_secret")
+    return [_pt(g1[t], 0) for t in range(K)], [_g2_tuple(g2[t], nl) for t in range(K + 1)]
+
+
+class KZGSubvectorKey:
+    """The verifying key of subvector proofs: [s^t]_1 for t < K and [s^t]_2 for t <= K (K =
+    len(g1_powers)) and the domain size. Every point is checked (VCError(VC_E_INVALID) otherwise);
+    that the powers belong to one s is not: the key is trusted input. Host code, no Engine."""
+
+    def __init__(self, g1_powers, g2_powers, size, curve="bn254"):
+        self.h = None
+        self.r, self.nl, cid = _curve_params(curve)
+        K = len(g1_powers)
+        if len(g2_powers) != K + 1 or any(P is None for P in g1_powers) or any(Q is None for Q in g2_powers):
+            raise ValueError("K powers in G1 and K + 1 in G2, none the identity")
+        g1, _ = _pt_arrays(g1_powers, self.nl)
+        g2 = np.stack([_g2_array(Q, self.nl)[0] for Q in g2_powers])
+        h = ctypes.c_void_p()
+        check(lib().vc_kzg_svk_new(cid, size, K, _p(np.ascontiguousarray(g1)), _p(np.ascontiguousarray(g2)),
+                                   ctypes.byref(h)), "kzg_svk_new")
+        self.h, self.size, self.K, self.curve = h, size, K, curve
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().vc_kzg_svk_free(self.h)
+            self.h = None
+
+    def verify(self, commitment, indexes, ys, proof):
+        """One proof (a point | None) that positions `indexes` of the vector committed to hold `ys`
+        (vc_kzg_verify_subvector) -> bool. VCError(VC_E_RANGE) above K indices, VCError(VC_E_INVALID)
+        for a repeated index or one outside the domain."""
+        cxy, cinf = _pt_arrays([commitment], self.nl)
+        pxy, pinf = _pt_arrays([proof], self.nl)
+        idx = np.ascontiguousarray(np.asarray(indexes, dtype=np.uint32))
+        y = ints_to_limbs([int(v) & _M256 for v in ys], 4) if len(ys) else np.zeros((1, 4), dtype=np.uint64)
+        if len(ys) != len(idx):
+            raise ValueError("one y per index")
+        res = ctypes.c_int()
+        check(lib().vc_kzg_verify_subvector(self.h, _p(cxy), int(cinf[0]), _p(idx), len(idx), _p(np.ascontiguousarray(y)),
+                                            _p(pxy), int(pinf[0]), ctypes.byref(res)), "kzg_verify_subvector")
+        return bool(res.value)
+
+
 def ipa_batch_challenge(seed):
     """rho of vc_ipa_verify_batch for a 32-byte seed: hash_to_field(seed, b"vkzg-ipa-batch")."""
     if len(seed) != 32:
@@ -641,6 +704,53 @@ class KZG:
                                       _p(row) if row is not None else None, _p(pts), n, _p(pxy), _p(pinf), _p(ys)),
               "kzg_prove_many")
         return [{"proof": _pt(pxy[i], pinf[i]), "y": limbs_to_int(ys[i])} for i in range(n)]
+
+    def prove_subvectors(self, rows, index_sets, datas):
+        """One subvector proof per index set (vc_kzg_prove_subvector_many): set s proves the positions
+        index_sets[s] of datas[rows[s]] (rows None: datas[s]) -> list of {"proof", "ys"}, the ys in the
+        set's own order. The reference's prove_batch (kzg/mod.rs:156-163, todo!() there)."""
+        n = len(index_sets)
+        if n == 0:
+            return []
+        width = len(datas[0].evals)
+        if any(len(d.evals) != width for d in datas):
+            raise ValueError("one batch proves data of one length")
+        ev = datas[0].limbs() if len(datas) == 1 else np.concatenate([d.limbs() for d in datas])
+        ev = np.ascontiguousarray(ev)
+        row = np.ascontiguousarray(np.asarray(rows, dtype=np.uint32)) if rows is not None else None
+        if row is not None and row.shape != (n,):
+            raise ValueError("rows: one data index per index set")
+        off = np.zeros(n + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(s) for s in index_sets])
+        total = int(off[n])
+        idx = np.ascontiguousarray(np.asarray([i for s in index_sets for i in s], dtype=np.uint32))
+        if idx.size == 0:
+            idx = np.zeros(1, dtype=np.uint32)
+        pxy = np.zeros((n, 2 * self.nl), dtype=np.uint64)
+        pinf = np.zeros(n, dtype=np.uint8)
+        ys = np.zeros((max(total, 1), 4), dtype=np.uint64)
+        check(lib().vc_kzg_prove_subvector_many(self.engine.h, self.table, self.size, len(datas), width, _p(ev),
+                                                _p(row) if row is not None else None, _p(off), _p(idx), n, _p(pxy),
+                                                _p(pinf), _p(ys)), "kzg_prove_subvector_many")
+        return [{"proof": _pt(pxy[s], pinf[s]), "ys": [limbs_to_int(ys[p]) for p in range(int(off[s]), int(off[s + 1]))]}
+                for s in range(n)]
+
+    def prove_subvector(self, commitment, indexes, data):
+        """prove_batch(key, commitment, indexes, data): one proof for the positions `indexes` of data;
+        the commitment is unused, as in prove_point."""
+        return self.prove_subvectors(None, [list(indexes)], [data])[0]
+
+    def g1_powers(self, K):
+        """[s^t]_1 for t < K from the Lagrange SRS (vc_kzg_g1_powers), no secret."""
+        out = np.zeros((K, 2 * self.nl), dtype=np.uint64)
+        check(lib().vc_kzg_g1_powers(self.engine.h, self.table, self.size, K, _p(out)), "kzg_g1_powers")
+        return [_pt(out[t], 0) for t in range(K)]
+
+    def subvector_key(self, K):
+        """The KZGSubvectorKey for sets of up to K indices: G1 powers from the SRS on the GPU, G2
+        powers from the setup's secret (as g2())."""
+        _, g2 = kzg_powers_from_secret(self.secret, K, self.engine.curve)
+        return KZGSubvectorKey(self.g1_powers(K), g2, self.size, self.engine.curve)
 
     def prove_all_points(self, data, mode=0):
         """KZG::prove_all_points (kzg/mod.rs:200-235) -- mode 0: the reference's computation
