@@ -448,6 +448,50 @@ void vc_kzg_svk_free(vc_kzg_svk* svk);
 int vc_kzg_verify_subvector(const vc_kzg_svk* svk, const uint64_t* com_xy, uint8_t com_inf, const uint32_t* idx,
                             size_t k, const uint64_t* y, const uint64_t* proof_xy, uint8_t proof_inf, int* result);
 
+/* ---------------------------------------------------------------- KZG subvector batch verification
+ * n subvector proofs (C_j, S_j, y_j, pi_j), one combined verdict: are all of them valid? With one
+ * challenge rho and the weights rho^j the coefficients of Z_j = sum_t z_{j,t} X^t and
+ * I_j = sum_t a_{j,t} X^t move onto the G1 side (Kmax = max_j |S_j|, z_{j,t} = 0 above |S_j|):
+ *   P_t = sum_j rho^j z_{j,t} pi_j (t = 0 .. Kmax),  a_t = sum_j rho^j a_{j,t} (t < Kmax),
+ *   P_H = P_0 + sum_t a_t [s^t]_1 - sum_j rho^j C_j,
+ *   accept  <=>  e(P_H, H) prod_{t = 1 .. Kmax} e(P_t, [s^t]_2) == 1.
+ * The left side is prod_j E_j^(rho^j), E_j the single verifier's product: a batch with an invalid
+ * entry is accepted for at most n - 1 values of rho (D(rho) = sum_j d_j rho^j). Every G2 point is a
+ * point of the key; their Miller lines are tabulated on the first batch call of a key (once,
+ * thread-safe; vc_kzg_svk_new makes none), and the check is one multi-Miller loop over the host pool
+ * with one final exponentiation.
+ *
+ * Layout, vc_kzg_prove_subvector_many's: com_xy / proof_xy n x 2 NL u64 with n identity flags,
+ * idx_off n + 1 u32, idx idx_off[n] u32, y idx_off[n] x 4 u64, y[p] belonging to idx[p].
+ * ctx: a context of the key's curve; the device path takes domains of 2 <= size <= 1024 (the
+ * prover's; VC_E_RANGE above). ctx == NULL: the same fold on the host pool, for any size the key takes
+ * (the check of the fold on a machine without a GPU, not a product path).
+ *
+ * Status, decided on the host before any GPU work, the outputs untouched: VC_E_INVALID for an index
+ * >= size, a repeated index inside one set, an empty set, a non-monotone idx_off, a null argument,
+ * rho >= r, a context whose curve is not the key's; VC_E_RANGE for a set of more than K indices.
+ * Malformed proof content -- a coordinate >= p, a point off the curve, a y >= r, on BLS12-381 a G1
+ * point outside the subgroup -- is *malformed = 1 (vc_kzg_subvector_batch_fold) or *result = 0
+ * (vc_kzg_verify_subvector_batch) with VC_OK. The identity flag is a valid C_j and a valid pi_j. */
+/* rho for a seed: hash_to_field(seed, dst = "vkzg-kzg-subv-batch") reduced mod the curve's r */
+int vc_kzg_subvector_batch_challenge(int curve, const uint8_t seed[32], uint64_t* rho_fr);
+/* The fold alone: *kmax_out = Kmax and Kmax + 1 canonical affine points with identity flags, P_H
+ * first, then P_1 .. P_Kmax (p_xy: room for (K + 1) x 2 NL u64, p_inf: K + 1). n == 0: Kmax = 0 and
+ * P_H the identity. With *malformed = 1 the points are not written. */
+int vc_kzg_subvector_batch_fold(vc_ctx* ctx, const vc_kzg_svk* svk, size_t n, const uint64_t* com_xy,
+                                const uint8_t* com_inf, const uint32_t* idx_off, const uint32_t* idx,
+                                const uint64_t* y, const uint64_t* proof_xy, const uint8_t* proof_inf,
+                                const uint64_t* rho_fr, size_t* kmax_out, uint64_t* p_xy, uint8_t* p_inf,
+                                int* malformed);
+/* *result = 1 when the combined check accepts. seed32: 32 bytes the verifier draws after it holds the
+ * inputs (a given seed makes the call deterministic); NULL draws OS entropy. results: NULL, or n
+ * bytes: all 1 on accept, vc_kzg_verify_subvector's verdicts (over the host pool; they need no
+ * context) on reject. n == 0: VC_OK with *result = 1. */
+int vc_kzg_verify_subvector_batch(vc_ctx* ctx, const vc_kzg_svk* svk, size_t n, const uint64_t* com_xy,
+                                  const uint8_t* com_inf, const uint32_t* idx_off, const uint32_t* idx,
+                                  const uint64_t* y, const uint64_t* proof_xy, const uint8_t* proof_inf,
+                                  const uint8_t* seed32, int* result, uint8_t* results);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,12 +20,6 @@
 using namespace vk;
 using namespace vk::ate;
 
-struct vc_kzg_svk {
-    size_t size = 0;  // the domain
-    size_t K = 0;     // g1: K powers, g2: K + 1
-    int curve = 0;
-};
-
 namespace {
 
 // ---------------------------------------------------------------- G2, Jacobian over Fq2 (a = 0)
@@ -126,37 +120,6 @@ bool index_set_ok(const uint32_t* idx, size_t k, size_t size) {
     if (s.back() >= size) return false;
     return std::adjacent_find(s.begin(), s.end()) == s.end();
 }
-// x_i = w^idx[i] and c_i = 1 / prod_{l != i} (x_i - x_l), one inversion for all (Montgomery)
-template <class Fr>
-void sub_weights(const fe<Fr>& omega, const uint32_t* idx, size_t k, std::vector<fe<Fr>>& x, std::vector<fe<Fr>>& c) {
-    x.resize(k);
-    c.resize(k);
-    for (size_t i = 0; i < k; i++) x[i] = fe_pow_u64<Fr>(omega, idx[i]);
-    std::vector<fe<Fr>> pre(k);
-    fe<Fr> run = fe_one<Fr>();
-    for (size_t i = 0; i < k; i++) {
-        fe<Fr> d = fe_one<Fr>();
-        for (size_t l = 0; l < k; l++)
-            if (l != i) d = fe_mul<Fr>(d, fe_sub<Fr>(x[i], x[l]));
-        c[i] = d;
-        pre[i] = run;
-        run = fe_mul<Fr>(run, d);
-    }
-    fe<Fr> inv = fe_inv_bin<Fr>(run);
-    for (size_t i = k; i-- > 0;) {
-        const fe<Fr> d = c[i];
-        c[i] = fe_mul<Fr>(inv, pre[i]);
-        inv = fe_mul<Fr>(inv, d);
-    }
-}
-
-template <class C>
-struct SubKey : vc_kzg_svk {
-    fe<typename C::Fr> omega;  // the domain's generator (Montgomery)
-    std::vector<SWAff<typename C::Fq>> g1;
-    std::vector<G2AffT<typename C::Fq>> g2;
-};
-
 template <class C>
 int weights(size_t N, const uint32_t* idx, size_t k, uint64_t* c_out) {
     using Fr = typename C::Fr;
@@ -277,11 +240,6 @@ int verify(const SubKey<C>& key, const uint64_t* com_xy, uint8_t com_inf, const 
     const G2AffT<Fq> Q[2] = {A, g2_generator<Fq>()};
     *result = pairing_product_is_one(2, P, Q) ? 1 : 0;
     return VC_OK;
-}
-
-template <class C>
-const SubKey<C>& sub_key(const vc_kzg_svk* k) {
-    return *static_cast<const SubKey<C>*>(k);
 }
 
 }  // namespace

@@ -417,6 +417,21 @@ VK_HD Fq12T<F> miller_loop_tab2(const G1EvalT<F>& P0, const LineCoefT<F>* tab0, 
     if constexpr (C::X_NEGATIVE) return fq12_conj(f);
     else return f;
 }
+// the same for m tables: prod_j of the Miller loops of P[j] over tab[j], one squaring chain for all
+// of them, identities skipped (m = 2 is miller_loop_tab2 step for step). The conjugation is a ring
+// automorphism, so the products of several calls multiply to the product over all their tables.
+template <class F>
+VK_HD Fq12T<F> miller_loop_tabn(int m, const G1EvalT<F>* P, const LineCoefT<F>* const* tab) {
+    using C = KzgCurve<F>;
+    Fq12T<F> f = fq12_one<F>();
+    for (int k = 0; k < C::PC::ATE_LINES; k++) {
+        if (C::PC::ate_sq(k)) f = fq12_sqr(f);
+        for (int j = 0; j < m; j++)
+            if (!P[j].skip) f = fq12_mul_line(f, tab[j][k], P[j]);
+    }
+    if constexpr (C::X_NEGATIVE) return fq12_conj(f);
+    else return f;
+}
 // (a + b s)^2 in Fq2[s]/(s^2 - xi): (a + b)(a + xi b) - ab - xi ab, 2 ab
 template <class F>
 VK_HD void fq4_sqr(const Fq2T<F>& a, const Fq2T<F>& b, Fq2T<F>& t0, Fq2T<F>& t1) {

@@ -8,6 +8,10 @@
 
 #include <string.h>
 
+#include <memory>
+#include <mutex>
+#include <vector>
+
 #include "host/fr.hpp"
 #include "pairing.hpp"
 #include "pairing_bls.hpp"
@@ -60,5 +64,56 @@ inline void g2_store(const ate::G2AffT<F>& p, uint64_t* xy, uint8_t* inf) {
     mont_to_canon<F>(p.x.c1, xy + NW);
     mont_to_canon<F>(p.y.c0, xy + 2 * NW);
     mont_to_canon<F>(p.y.c1, xy + 3 * NW);
+}
+}  // namespace vk
+
+// The key of subvector proofs (kzg_sub_host.cpp makes and frees it; kzg_subv.hip reads it too).
+struct vc_kzg_svk {
+    size_t size = 0;  // the domain
+    size_t K = 0;     // g1: K powers, g2: K + 1
+    int curve = 0;
+};
+
+namespace vk {
+template <class C>
+struct SubKey : vc_kzg_svk {
+    fe<typename C::Fr> omega;  // the domain's generator (Montgomery)
+    std::vector<SWAff<typename C::Fq>> g1;
+    std::vector<ate::G2AffT<typename C::Fq>> g2;
+    // Miller-loop lines of [s^t]_2 for the batch verifier alone: lines[t] is the table of [s^t]_2
+    // (t = 0: H), ATE_LINES entries. Made on first use and grown under the lock, each table an
+    // allocation of its own that never moves: a caller copies the pointers it needs while it holds
+    // the lock. vc_kzg_svk_new makes none of them.
+    mutable std::mutex lines_mu;
+    mutable std::vector<std::unique_ptr<ate::LineCoefT<typename C::Fq>[]>> lines;
+};
+// x_i = w^idx[i] and c_i = 1 / prod_{l != i} (x_i - x_l), one inversion for all (Montgomery):
+// the single verifier and the batch fold's host path
+template <class Fr>
+inline void sub_weights(const fe<Fr>& omega, const uint32_t* idx, size_t k, std::vector<fe<Fr>>& x,
+                        std::vector<fe<Fr>>& c) {
+    x.resize(k);
+    c.resize(k);
+    for (size_t i = 0; i < k; i++) x[i] = fe_pow_u64<Fr>(omega, idx[i]);
+    std::vector<fe<Fr>> pre(k);
+    fe<Fr> run = fe_one<Fr>();
+    for (size_t i = 0; i < k; i++) {
+        fe<Fr> d = fe_one<Fr>();
+        for (size_t l = 0; l < k; l++)
+            if (l != i) d = fe_mul<Fr>(d, fe_sub<Fr>(x[i], x[l]));
+        c[i] = d;
+        pre[i] = run;
+        run = fe_mul<Fr>(run, d);
+    }
+    fe<Fr> inv = fe_inv_bin<Fr>(run);
+    for (size_t i = k; i-- > 0;) {
+        const fe<Fr> d = c[i];
+        c[i] = fe_mul<Fr>(inv, pre[i]);
+        inv = fe_mul<Fr>(inv, d);
+    }
+}
+template <class C>
+inline const SubKey<C>& sub_key(const vc_kzg_svk* k) {
+    return *static_cast<const SubKey<C>*>(k);
 }
 }  // namespace vk

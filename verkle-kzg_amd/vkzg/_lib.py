@@ -112,6 +112,11 @@ SIGNATURES = {
     "vc_kzg_svk_free": (None, [c_void_p]),
     "vc_kzg_verify_subvector": (c_int, [c_void_p, P, ctypes.c_uint8, P, c_size_t, P, P, ctypes.c_uint8,
                                         ctypes.POINTER(c_int)]),
+    "vc_kzg_subvector_batch_challenge": (c_int, [c_int, P, P]),
+    "vc_kzg_subvector_batch_fold": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P, P,
+                                            ctypes.POINTER(c_size_t), P, P, ctypes.POINTER(c_int)]),
+    "vc_kzg_verify_subvector_batch": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P, P,
+                                              ctypes.POINTER(c_int), P]),
     "vc_kzg_quotient": (c_int, [c_void_p, c_size_t, P, c_size_t, P, P, P]),
     "vc_kzg_prove_all_points": (c_int, [c_void_p, c_int, c_size_t, P, c_size_t, c_int, P, P, P,
                                         ctypes.POINTER(c_size_t)]),

@@ -595,7 +595,8 @@ def kzg_powers_from_secret(secret, K, curve="bn254"):
 class KZGSubvectorKey:
     """The verifying key of subvector proofs: [s^t]_1 for t < K and [s^t]_2 for t <= K (K =
     len(g1_powers)) and the domain size. Every point is checked (VCError(VC_E_INVALID) otherwise);
-    that the powers belong to one s is not: the key is trusted input. Host code, no Engine."""
+    that the powers belong to one s is not: the key is trusted input. Host code, no Engine, except
+    verify_batch / batch_fold when given one (of the key's curve)."""
 
     def __init__(self, g1_powers, g2_powers, size, curve="bn254"):
         self.h = None
@@ -629,6 +630,73 @@ class KZGSubvectorKey:
         check(lib().vc_kzg_verify_subvector(self.h, _p(cxy), int(cinf[0]), _p(idx), len(idx), _p(np.ascontiguousarray(y)),
                                             _p(pxy), int(pinf[0]), ctypes.byref(res)), "kzg_verify_subvector")
         return bool(res.value)
+
+
+    def _subv_arrays(self, commitments, index_sets, ys, proofs):
+        n = len(proofs)
+        if not (len(commitments) == len(index_sets) == len(ys) == n):
+            raise ValueError("one commitment, index set and list of ys per proof")
+        if any(len(S) != len(v) for S, v in zip(index_sets, ys)):
+            raise ValueError("one y per index")
+        cxy, cinf = _pt_arrays(commitments, self.nl)
+        pxy, pinf = _pt_arrays(proofs, self.nl)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(S) for S in index_sets])
+        idx = np.ascontiguousarray(np.asarray([i for S in index_sets for i in S], dtype=np.uint32))
+        flat = [int(v) & _M256 for yv in ys for v in yv]
+        if idx.size == 0:
+            idx = np.zeros(1, dtype=np.uint32)
+        y = np.ascontiguousarray(ints_to_limbs(flat, 4)) if flat else np.zeros((1, 4), dtype=np.uint64)
+        return cxy, cinf, off, idx, y, pxy, pinf
+
+    def batch_fold(self, engine, commitments, index_sets, ys, proofs, rho):
+        """The fold of verify_batch alone (vc_kzg_subvector_batch_fold): [P_H, P_1 .. P_Kmax] for the
+        challenge rho (Kmax the largest set), or None when an entry is malformed. engine None: the
+        host path."""
+        n = len(proofs)
+        a = self._subv_arrays(commitments, index_sets, ys, proofs) if n else (None,) * 7
+        ptr = [_p(x) if x is not None else None for x in a]
+        out = np.zeros((self.K + 1, 2 * self.nl), dtype=np.uint64)
+        inf = np.zeros(self.K + 1, dtype=np.uint8)
+        bad, kmax = ctypes.c_int(), ctypes.c_size_t()
+        check(lib().vc_kzg_subvector_batch_fold(engine.h if engine is not None else None, self.h, n, *ptr,
+                                                _p(_fr_raw(rho)), ctypes.byref(kmax), _p(out), _p(inf),
+                                                ctypes.byref(bad)), "kzg_subvector_batch_fold")
+        if bad.value:
+            return None
+        return [_pt(out[t], inf[t]) for t in range(kmax.value + 1)]
+
+    def verify_batch(self, engine, commitments, index_sets, ys, proofs, seed=None, locate=False):
+        """One combined check for n subvector proofs (vc_kzg_verify_subvector_batch) -> bool: are all
+        of them valid? proofs: points | None. seed: 32 bytes the verifier draws after it holds the
+        inputs (None: OS entropy). locate=True -> (bool, list of bool): when the combined check
+        rejects, verify's verdicts say which ones are bad. engine None: the host path."""
+        n = len(proofs)
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        a = self._subv_arrays(commitments, index_sets, ys, proofs) if n else (None,) * 7
+        ptr = [_p(x) if x is not None else None for x in a]
+        s = np.frombuffer(bytes(seed), dtype=np.uint8).copy() if seed is not None else None
+        out = np.zeros(max(n, 1), dtype=np.uint8) if locate else None
+        res = ctypes.c_int()
+        check(lib().vc_kzg_verify_subvector_batch(engine.h if engine is not None else None, self.h, n, *ptr,
+                                                  _p(s) if s is not None else None, ctypes.byref(res),
+                                                  _p(out) if locate else None), "kzg_verify_subvector_batch")
+        if locate:
+            return bool(res.value), [bool(v) for v in out[:n]]
+        return bool(res.value)
+
+
+def kzg_subvector_batch_challenge(seed, curve="bn254"):
+    """rho of KZGSubvectorKey.verify_batch for a 32-byte seed: hash_to_field(seed,
+    b"vkzg-kzg-subv-batch") mod the curve's r."""
+    if len(seed) != 32:
+        raise ValueError("seed: 32 bytes")
+    _, _, cid = _curve_params(curve)
+    s = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+    out = np.zeros(4, dtype=np.uint64)
+    check(lib().vc_kzg_subvector_batch_challenge(cid, _p(s), _p(out)), "kzg_subvector_batch_challenge")
+    return limbs_to_int(out)
 
 
 def ipa_batch_challenge(seed):
