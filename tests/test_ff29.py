@@ -81,7 +81,7 @@ def test_ff29_zero_test(lines):
 
 @pytest.mark.parametrize("lz,ch", [(3, 16), (4, 16), (4, 32), (6, 24)])
 def test_mp_chunk_lazy_reduction_bn254_fr(lz, ch):
-    """k_mp_chunk's arithmetic (csrc/scheme.hip; 4 x 16 is the built LZ x CH shape) restated with
+    """k_mp_chunk's arithmetic (csrc/multiproof.hip; 4 x 16 is the built LZ x CH shape) restated with
     Python integers: evaluations f (canonical) times r^i R' (radix-2^29 Montgomery, R' = 2^261)
     added into 17 64-bit columns for up to LZ queries, one Montgomery reduction per LZ, the block
     results added with one conditional subtraction each -- == sum f_i r^i mod r for chunks of

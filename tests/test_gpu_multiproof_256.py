@@ -1,7 +1,7 @@
 """configs[4] at the reference's own shape, checked against the oracle: prove_multiproof
 (vector-commit/src/multiproof.rs:99-176) at width N = 256 (benches/ipa.rs:18) with Q = 4096 and
 Q = 2^16 queries (:19, 111-131). Every row z holds many queries, which is the multi-chunk path of
-the engine's per-point sums (MP_CHUNK = 16 queries per chunk, csrc/scheme.hip) and its large-Q
+the engine's per-point sums (MP_CHUNK = 16 queries per chunk, csrc/multiproof.hip) and its large-Q
 row grouping.
 
 The checker is oracle/pyoracle/mpcheck.py: r and t from the oracle's TranscriptHasher, g and h

@@ -78,6 +78,42 @@ def test_ipa_batched_proofs_match_single(eng, crs):
         assert ipa.verify_point(coms[i], pts[i], batch[i])
 
 
+@pytest.fixture(scope="module")
+def ipa8_case(eng, crs):
+    """33 openings at N = 8 (three rounds: the coefficients are folded twice): indices in the domain,
+    values outside it, one point twice; with each the proof of a call of its own and the oracle's"""
+    from pyoracle import protocol
+    from vkzg import scheme
+    ipa = scheme.IPA(eng, 8, crs[:9])
+    oracle = protocol.IPA(8, points=crs[:9])
+    rng = random.Random(19)
+    datas = [scheme.LagrangeBasis([rng.randrange(scheme.R_BN254) for _ in range(8)]) for _ in range(33)]
+    coms = list(ipa.commit_batch(datas))
+    pts = [(i % 8) if i % 2 == 0 else rng.randrange(8, scheme.R_BN254) for i in range(33)]
+    pts[5], pts[6] = 8, 2 ** 200 + 7  # the first value that is no index, and one far above 64 bits
+    pts[32], datas[32], coms[32] = pts[1], datas[1], coms[1]  # the repeated opening
+    single = [ipa.prove_point(coms[i], pts[i], datas[i]).as_dict() for i in range(33)]
+    want = [oracle.prove_point(coms[i], pts[i], protocol.LagrangeBasis.from_vec(list(datas[i].evals)))
+            for i in range(33)]
+    return ipa, datas, coms, pts, single, want
+
+
+@pytest.mark.parametrize("B", [33, 32])
+def test_ipa_batch_rows_on_host_and_on_device(ipa8_case, B):
+    """vc_ipa_prove builds the rounds' rows on the host when the 2 B commits of a round are more
+    than the commit engine's latency path takes (64): B = 33 is the first such batch, B = 32 the
+    largest that may keep the rows on the device. Either way every proof is, byte for byte, the proof
+    of a call of its own (B = 1, rows on the device) and the oracle's, and verifies."""
+    ipa, datas, coms, pts, single, want = ipa8_case
+    batch = ipa.prove_batch_points(coms[:B], pts[:B], datas[:B])
+    assert len(batch) == B
+    for i in range(B):
+        got = batch[i].as_dict()
+        assert got == single[i], i
+        assert got == want[i], i
+        assert ipa.verify_point(coms[i], pts[i], batch[i]), i
+
+
 def test_reference_ipa_eval_test(eng, crs):
     """ipa/mod.rs:404-421 at N = 32 with data 0..31."""
     from pyoracle import protocol

@@ -346,7 +346,7 @@ int vc_multiproof_prove_sharded(vc_ctx* ctx, vc_comm* comm, int scheme, int tabl
     // this rank's share up to the exchange; its status is agreed on before the device all-gather
     // (a rank without its S buffer cannot enter that collective)
     // rows of S = the distinct z (validated here, as the begin call would)
-    int st = vk::mp_rows(N, Q, z, &rows);
+    int st = vc_multiproof_rows(N, Q, z, &rows);
     const size_t sbytes = rows * N * 32;
     uint8_t* dS = nullptr;
     if (st == VC_OK) {
@@ -355,8 +355,8 @@ int vc_multiproof_prove_sharded(vc_ctx* ctx, vc_comm* comm, int scheme, int tabl
         st = comm->work.ensure(sbytes * (comm->world + 1));
         if (st == VC_OK) {
             dS = reinterpret_cast<uint8_t*>(comm->work.p);
-            // the host transcript overlapped with the shard's plan (scheme.hip mp_begin_accumulate)
-            st = vk::mp_begin_accumulate(ctx, N, Q, com_xy, com_inf, z, y, lo, hi - lo, d_data_slice, dS, &tr, r);
+            // the host transcript overlapped with the shard's plan (vc_multiproof_begin_accumulate)
+            st = vc_multiproof_begin_accumulate(ctx, N, Q, com_xy, com_inf, z, y, lo, hi - lo, d_data_slice, dS, &tr, r);
         }
     }
     st = agree(comm, ctx, st);

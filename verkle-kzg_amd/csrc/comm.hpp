@@ -36,7 +36,7 @@ struct Multi {
 // members write into the one tree's level records directly)
 int verkle_commitment(vc_ctx* ctx, int table, vc_verkle* t, uint64_t* out_xy, uint8_t* out_inf, const Shard* sh,
                       const Multi* mu = nullptr);
-// KZG::prove_point split by index range (scheme.hip): share [lo, hi) of the domain uploads only
+// KZG::prove_point split by index range (kzg_open.hip): share [lo, hi) of the domain uploads only
 // its evaluations, phase 1 returns its partial of the one global sum (4 u64: Montgomery Fr words),
 // phase 2 takes the members' total (kzg_share_sum) and returns the MSM accumulator over SRS points
 // [lo, hi) and y (canonical)

@@ -2,7 +2,7 @@
 // one source: the kernels of ipa_verify.hip are thin wrappers over it, and tests/cpp/
 // ipa_verify_check.cpp runs the same text on the host.
 //
-// low_level_verify_ipa (ipa/mod.rs:321-360) as one identity, the one ipa_verify_impl (scheme.hip)
+// low_level_verify_ipa (ipa/mod.rs:321-360) as one identity, the one ipa_verify_impl (ipa.hip)
 // checks: with challenges w and x_0..x_{K-1}, s = points_coeffs, b = the barycentric weights of
 // the point and P_k = prod_{j>k} x_j,
 //   (prod x) C + sum_k (P_k L_k + P_k x_k^2 R_k) + sum_i (-tip s_i) g_i

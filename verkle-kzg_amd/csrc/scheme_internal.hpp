@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include <functional>
+#include <vector>
 
 #include "../../include/vc_scheme.h"
 #include "host/fr.hpp"
@@ -38,13 +39,31 @@ Fr to_data_item_host(const uint64_t* xy, bool inf);
 void ipa_host_challenges(size_t lo, size_t cnt, int K, const uint64_t* com_xy, const uint8_t* com_inf,
                          const uint64_t* points, const uint64_t* y, const uint64_t* l_xy, const uint8_t* l_inf,
                          const uint64_t* r_xy, const uint8_t* r_inf, vc_transcript** transcripts, Fr* chal);
-// vc_multiproof_begin + vc_multiproof_accumulate of the query shard [first, first + Qs), the host
-// transcript on a helper thread while this thread plans the shard (scheme.hip); r_out canonical
-// the number of distinct z (rows of the per-point sums); VC_E_DOMAIN for z >= N
-int mp_rows(size_t N, size_t Q, const uint64_t* z, size_t* rows);
-int mp_begin_accumulate(vc_ctx* ctx, size_t N, size_t Q, const uint64_t* com_xy, const uint8_t* com_inf,
-                        const uint64_t* z, const uint64_t* y, size_t first, size_t Qs, const void* d_data, void* d_S,
-                        vc_transcript** tr_out, uint64_t* r_out);
+
+// ---- host helpers of the protocol layer, BN254 (scheme.hip describes them)
+struct Table;
+BN254G1::Acc acc_of(const uint64_t* xy, bool inf);  // canonical affine (or the identity) -> accumulator
+void aff_of(const BN254G1::Acc& a, uint64_t* xy, uint8_t* inf);
+std::vector<Fr> host_batch_inv(const std::vector<Fr>& v);  // 1 / 0 = 0
+std::vector<Fr> barycentric(size_t size, const Fr& point, const Fr& omega);
+bool barycentric_panics(size_t size, const Fr& point);
+int commit_batch(vc_ctx* ctx, Table* t, size_t width, const Fr* sc, size_t batch, uint64_t* out_xy, uint8_t* out_inf,
+                 const std::function<void()>* overlap = nullptr);
+constexpr size_t HOST_MSM_MAX = 64;
+int host_msm(const uint64_t* xy, const uint8_t* inf, const Fr* sc, size_t n, BN254G1::Acc* out);
+int msm_points(vc_ctx* ctx, const uint64_t* xy, const uint8_t* inf, const std::vector<Fr>& sc, BN254G1::Acc* out,
+               bool filled = false);
+
+// ---- what the multiproof takes from the other protocols
+// trs: NULL, or per proof NULL (a fresh "ipa") or the transcript to continue (ipa.hip)
+int ipa_prove_impl(vc_ctx* ctx, Table* t, size_t N, const std::vector<std::vector<Fr>>& data,
+                   const std::vector<BN254G1::Acc>& coms, const std::vector<Fr>& points, vc_transcript** trs,
+                   vc_ipa_proof* proofs);
+int ipa_verify_impl(vc_ctx* ctx, Table* t, size_t N, const BN254G1::Acc& com, const Fr& point, const vc_ipa_proof* pr,
+                    vc_transcript* tr_in, int* result);
+// the BN254 opening of `size` canonical host evaluations at a canonical point (kzg_open.hip)
+int kzg_open_bn254(vc_ctx* ctx, Table* t, size_t size, const uint64_t* evals, const uint64_t* point,
+                   uint64_t* proof_xy, uint8_t* proof_inf, uint64_t* y);
 
 // A multiproof whose evaluation rows are sparse and already (mostly) on the device -- the verkle
 // tree proofs (verkle.cpp): the per-point sums S[row(z_i)][k] += r^i f_i[k] are accumulated from the
