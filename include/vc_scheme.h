@@ -84,6 +84,38 @@ int vc_ipa_commit(vc_ctx* ctx, int table, size_t N, const uint64_t* data, size_t
 int vc_ipa_prove(vc_ctx* ctx, int table, size_t N, const uint64_t* data, const uint64_t* com_xy,
                  const uint8_t* com_inf, const uint64_t* points, size_t batch,
                  vc_transcript** transcripts, vc_ipa_proof* proofs);
+/* n openings in one call, the whole proof made on the device (the reference's prove_batch,
+ * ipa/mod.rs:156-163, is todo!(); its BatchProof is Vec<Proof>). Opening i is prove_point of row
+ * row[i] of `data` (rows x N canonical values; row == NULL: row i, and then rows == n) at
+ * points[i] (n x 4) over a fresh "ipa" transcript; callers with prior transcript state keep using
+ * vc_ipa_prove. The row's commitment is com_xy + 8 row[i], com_inf[row[i]] (per row, as
+ * vc_ipa_commit gives them; not checked against the data, as in vc_ipa_prove). Outputs are the flat
+ * layouts vc_ipa_verify_many / vc_ipa_verify_batch read, K = log2 N: l_xy / r_xy n x K x 8,
+ * l_inf / r_inf n x K, tip and y n x 4 -- a batch goes from prover to verifier without repacking.
+ * Opening i equals, bit for bit, what vc_ipa_prove(ctx, table, N, data + row[i] N 4, .., points +
+ * 4 i, 1, NULL, ..) writes.
+ * Every status other than VC_OK is decided on the host before any GPU work, the outputs untouched.
+ * VC_E_INVALID: N not a power of two or outside [2, 256] (vc_ipa_verify_batch's bound: a wave's
+ * share of a row is four entries per lane), a context that is not BN254, a null array with n > 0,
+ * row == NULL with rows != n, a row[i] >= rows, a point >= r, a table of fewer than N + 1 points.
+ * VC_E_TABLE: an unknown table. VC_E_DOMAIN for the whole call when a point is a domain element
+ * w^i that is not below N as an integer (as vc_ipa_prove treats a batch). n = 0 is VC_OK.
+ * The rows are uploaded once; per chunk of at most 8192 openings the weights, the transcripts, the
+ * folds and the rounds' scalar rows are made by kernels and committed by the fixed-base engine
+ * with nothing of the proof crossing to the host between the rounds (the commit's own
+ * normalisation aside): the device workspace does not grow with n. Throughput-
+ * shaped: a batch of one pays the whole pipeline's launches and is slower than vc_ipa_prove. */
+int vc_ipa_prove_many(vc_ctx* ctx, int table, size_t N, size_t rows, const uint64_t* data,
+                      const uint32_t* row, const uint64_t* com_xy, const uint8_t* com_inf,
+                      const uint64_t* points, size_t n,
+                      uint64_t* l_xy, uint8_t* l_inf, uint64_t* r_xy, uint8_t* r_inf,
+                      uint64_t* tip, uint64_t* y);
+/* the same with the rows already in device memory (rows x N x 4 u64, canonical; not written) */
+int vc_ipa_prove_many_device(vc_ctx* ctx, int table, size_t N, size_t rows, const void* d_data,
+                             const uint32_t* row, const uint64_t* com_xy, const uint8_t* com_inf,
+                             const uint64_t* points, size_t n,
+                             uint64_t* l_xy, uint8_t* l_inf, uint64_t* r_xy, uint8_t* r_inf,
+                             uint64_t* tip, uint64_t* y);
 /* verify_point (:165-181 -> low_level_verify_ipa :321-360); result 1 = valid, 0 = invalid */
 int vc_ipa_verify(vc_ctx* ctx, int table, size_t N, const uint64_t* com_xy, uint8_t com_inf,
                   const uint64_t* point, const vc_ipa_proof* proof, vc_transcript* transcript,

@@ -31,20 +31,35 @@ inline void q_terms(const FrE* a, const FrE* b, const FrE& w, size_t half, FrE* 
     *qR = fe_mul<BN254Fr>(w, inner(a + half, b, half));
 }
 
+// ---- the rows and the fold entry by entry (host and device: csrc/ipa_many.hpp's lanes take one
+// entry each, the loops below take them all)
+// whether CRS point i of a round of width m (half = m / 2) belongs to L's row (else to R's)
+VK_HD bool row_is_left(size_t i, size_t m, size_t half) { return (i % m) >= half; }
+// the entry of a that CRS point i multiplies in its row: a_L for L's bases, a_R for R's
+VK_HD size_t row_source(size_t i, size_t m, size_t half) {
+    const size_t j = i % m;
+    return j >= half ? j - half : j + half;
+}
+// whether the fold of a round of width m multiplies coefficient i by the challenge
+VK_HD bool coeff_folds(size_t i, size_t m, size_t half) { return (i % m) < half; }
+VK_HD FrE fold_a_at(const FrE& x, const FrE& a_lo, const FrE& a_hi) {  // a_L + x a_R
+    return fe_add<BN254Fr>(a_lo, fe_mul<BN254Fr>(x, a_hi));
+}
+VK_HD FrE fold_b_at(const FrE& x, const FrE& b_lo, const FrE& b_hi) {  // b_R + x b_L
+    return fe_add<BN254Fr>(b_hi, fe_mul<BN254Fr>(x, b_lo));
+}
+
 // One round's rows of one proof, sL[0..N) and sR[0..N): L = <gens_R, a_L> takes the bases with
 // i mod m >= half, R = <gens_L, a_R> the others. coeff == nullptr: every coefficient is one (round
 // 0 -- the rows are a's halves as they are, no multiply). With b (and w) the q terms go to index N.
 inline void round_rows(const FrE* a, const FrE* coeff, size_t N, size_t m, size_t half, FrE* sL, FrE* sR,
                        const FrE* b = nullptr, const FrE* w = nullptr) {
     for (size_t i = 0; i < N; i++) {
-        const size_t j = i % m;
-        if (j >= half) {
-            sL[i] = coeff ? fe_mul<BN254Fr>(a[j - half], coeff[i]) : a[j - half];
-            sR[i] = fe_zero<BN254Fr>();
-        } else {
-            sR[i] = coeff ? fe_mul<BN254Fr>(a[j + half], coeff[i]) : a[j + half];
-            sL[i] = fe_zero<BN254Fr>();
-        }
+        const FrE& src = a[row_source(i, m, half)];
+        const FrE v = coeff ? fe_mul<BN254Fr>(src, coeff[i]) : src;
+        const bool left = row_is_left(i, m, half);
+        sL[i] = left ? v : fe_zero<BN254Fr>();
+        sR[i] = left ? fe_zero<BN254Fr>() : v;
     }
     if (b) q_terms(a, b, *w, half, &sL[N], &sR[N]);
 }
@@ -54,14 +69,14 @@ inline void round_rows(const FrE* a, const FrE* coeff, size_t N, size_t m, size_
 inline void round_fold(const FrE& x, size_t N, size_t m, size_t half, std::vector<FrE>& a, std::vector<FrE>* b,
                        FrE* coeff) {
     for (size_t j = 0; j < half; j++) {
-        a[j] = fe_add<BN254Fr>(a[j], fe_mul<BN254Fr>(x, a[j + half]));
-        if (b) (*b)[j] = fe_add<BN254Fr>((*b)[j + half], fe_mul<BN254Fr>(x, (*b)[j]));
+        a[j] = fold_a_at(x, a[j], a[j + half]);
+        if (b) (*b)[j] = fold_b_at(x, (*b)[j], (*b)[j + half]);
     }
     a.resize(half);
     if (b) b->resize(half);
     if (coeff)
         for (size_t i = 0; i < N; i++)
-            if ((i % m) < half) coeff[i] = fe_mul<BN254Fr>(coeff[i], x);
+            if (coeff_folds(i, m, half)) coeff[i] = fe_mul<BN254Fr>(coeff[i], x);
 }
 
 // The verifier's scalars from the challenges xs[0..K), Montgomery: s = points_coeffs ([1] -> each

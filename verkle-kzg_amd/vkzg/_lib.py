@@ -90,6 +90,9 @@ SIGNATURES = {
     "vc_ipa_prove": (c_int, [c_void_p, c_int, c_size_t, P, P, P, P, c_size_t, P, P]),
     "vc_ipa_verify": (c_int, [c_void_p, c_int, c_size_t, P, ctypes.c_uint8, P, P, c_void_p, ctypes.POINTER(c_int)]),
     "vc_ipa_verify_many": (c_int, [c_void_p, c_int, c_size_t, c_size_t, P, P, P, P, P, P, P, P, P, P, P]),
+    "vc_ipa_prove_many": (c_int, [c_void_p, c_int, c_size_t, c_size_t, P, P, P, P, P, c_size_t, P, P, P, P, P, P]),
+    "vc_ipa_prove_many_device": (c_int, [c_void_p, c_int, c_size_t, c_size_t, P, P, P, P, P, c_size_t, P, P, P, P, P,
+                                         P]),
     "vc_ipa_batch_challenge": (c_int, [P, P]),
     "vc_ipa_challenges_many": (c_int, [c_void_p, c_size_t, c_size_t, P, P, P, P, P, P, P, P, P]),
     "vc_ipa_batch_fold": (c_int, [c_void_p, c_int, P, c_size_t, c_size_t, P, P, P, P, P, P, P, P, P, P, P, P, P,

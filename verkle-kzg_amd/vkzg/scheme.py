@@ -285,6 +285,40 @@ class IPA:
               "ipa_prove")
         return [IPAProof._from(arr[i], bufs[i][1]) for i in range(B)]
 
+    def prove_many(self, commitments, points, datas, rows=None):
+        """n openings in one call, every round on the device (vc_ipa_prove_many): opening i is
+        prove_point of datas[rows[i]] (rows None: datas[i], one data per point) at points[i] over a
+        fresh "ipa" transcript -> list of IPAProof, equal to prove_point's. commitments: one per
+        data row. VCError(VC_E_DOMAIN) for the whole call when one point makes prove_point fail."""
+        n = len(points)
+        if n == 0:
+            return []
+        if len(commitments) != len(datas):
+            raise ValueError("commitments: one per data row")
+        d = datas[0].limbs(self.N)[: self.N] if len(datas) == 1 else np.concatenate([x.limbs(self.N)[: self.N] for x in datas])
+        d = np.ascontiguousarray(d)
+        cxy, cinf = _pt_arrays_many(commitments)
+        pts = ints_to_limbs([int(p) % R_BN254 for p in points], 4)
+        row = np.ascontiguousarray(np.asarray(rows, dtype=np.uint32)) if rows is not None else None
+        if row is not None and row.shape != (n,):
+            raise ValueError("rows: one data index per point")
+        K = _log2(self.N)
+        lxy, rxy = np.zeros((n * K, 8), dtype=np.uint64), np.zeros((n * K, 8), dtype=np.uint64)
+        linf, rinf = np.zeros(n * K, dtype=np.uint8), np.zeros(n * K, dtype=np.uint8)
+        tip, y = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        check(lib().vc_ipa_prove_many(self.engine.h, self.table, self.N, len(datas), _p(d),
+                                      _p(row) if row is not None else None, _p(cxy), _p(cinf), _p(pts), n,
+                                      _p(lxy), _p(linf), _p(rxy), _p(rinf), _p(tip), _p(y)), "ipa_prove_many")
+        fb = int.from_bytes
+        lraw, rraw, traw, yraw = lxy.tobytes(), rxy.tobytes(), tip.tobytes(), y.tobytes()
+        lflag, rflag = linf.tolist(), rinf.tolist()
+
+        def pts_of(raw, flags, i):
+            return [None if flags[j] else (fb(raw[64 * j:64 * j + 32], "little"), fb(raw[64 * j + 32:64 * j + 64], "little"))
+                    for j in range(i * K, (i + 1) * K)]
+        return [IPAProof(pts_of(lraw, lflag, i), pts_of(rraw, rflag, i), fb(traw[32 * i:32 * i + 32], "little"),
+                         fb(yraw[32 * i:32 * i + 32], "little")) for i in range(n)]
+
     def prove(self, commitment, index, data):
         return self.prove_point(commitment, index, data)
 
