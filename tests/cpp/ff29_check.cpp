@@ -88,5 +88,6 @@ int main() {
     run<F29BLS381Fq, BLS381Fq>("bls12_381_fq");
     run<F29BN254Fq, BN254Fq>("bn254_fq");
     run<F29BLS381Fr, BLS381Fr>("bls12_381_fr");
+    run<F29BN254Fr, BN254Fr>("bn254_fr");  // the limb set multiproof.hip multiplies with
     return 0;
 }

@@ -9,16 +9,9 @@ import subprocess
 
 import pytest
 
+from limb_bounds import check30
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
-L = 13
-RP = 1 << (30 * L)
-R32 = 1 << 384
-H = 1 << 29
-
-
-def val(limbs):
-    return sum(v << (30 * j) for j, v in enumerate(limbs))
 
 
 @pytest.fixture(scope="module")
@@ -30,42 +23,11 @@ def lines(tmp_path_factory):
     return [json.loads(ln) for ln in out.splitlines()]
 
 
-def exact(limbs):
-    return all(-H <= v < H for v in limbs[:-1])
-
-
-def near(limbs):
-    return all(-H - 2 <= v < H + 2 for v in limbs[:-1])
-
-
 def test_ff30_field_ops(lines):
     seen = set()
     for d in lines:
-        op = d["op"]
-        seen.add(op)
-        if op == "mul":
-            a, b, r = val(d["a"]), val(d["b"]), val(d["r"])
-            assert (r * RP - a * b) % P == 0
-            assert abs(r) < abs(a * b) // RP + P // 2 + (P >> 29)
-            assert exact(d["r"])
-        elif op == "mul2":
-            s = val(d["a"]) * val(d["b"]) + val(d["c"]) * val(d["d"])
-            r = val(d["r"])
-            assert (r * RP - s) % P == 0
-            assert abs(r) < abs(s) // RP + P // 2 + (P >> 29)
-            assert exact(d["r"])
-        elif op == "add" and "r" in d:
-            assert val(d["r"]) == val(d["a"]) + val(d["b"]) and near(d["r"])
-        elif op == "sub":
-            assert val(d["r"]) == val(d["a"]) - val(d["b"]) and near(d["r"])
-        elif op == "canon":
-            r = sum(v << (30 * j) for j, v in enumerate(d["r"]))
-            assert 0 <= r < P and (r - val(d["a"])) % P == 0
-        elif op == "mont":
-            a = sum(w << (32 * k) for k, w in enumerate(d["a"]))
-            back = sum(w << (32 * k) for k, w in enumerate(d["back"]))
-            assert back == a
-            assert (val(d["r"]) - a * RP * pow(R32, -1, P)) % P == 0
+        seen.add(d["op"])
+        check30(d)
     assert {"mul", "mul2", "add", "sub", "canon", "mont"} <= seen
 
 
