@@ -3,7 +3,7 @@ oracle's recursive gen_commitment (reference verkle-tree/src/node.rs:205-277, li
 
 At N = 32 the extension rows are 32 wide and the stem item `bytes_to_item(stem)`
 (node.rs:248-250 -> vector-commit/src/lagrange_basis.rs:175-176) really reduces mod r: the stems
-of tests/verkle32_keys.py cover every quotient estimate of verkle.cpp's item_of_bytes (k r - 1,
+of tests/verkle32_keys.py cover every quotient estimate of verkle_trie.hpp's item_of_bytes (k r - 1,
 k r, k r + 1 for k = 1..5, 2^256 - 1, stems below k r with k r's top limb) and random stems >= r;
 leaf units < 16 and >= 16 fill c1 and c2 (node.rs:226-239). Each tree is committed fresh, then
 after two update rounds (~1 % of the keys rewritten plus a few new keys: dirty nodes only, delta

@@ -3,7 +3,7 @@
 At N = 32 the stem is the whole 32-byte key (lib.rs:61-67, node.rs:45) and the extension's
 `stem_item = bytes_to_item(stem)` (node.rs:248-250 -> lagrange_basis.rs:175-176,
 from_le_bytes_mod_order) really reduces: a random stem is >= r whenever its top byte is >= 0x31
-(r = 0x30644e72... x 2^192). The engine's reduction (verkle.cpp item_of_bytes) takes one quotient
+(r = 0x30644e72... x 2^192). The engine's reduction (verkle_trie.hpp item_of_bytes) takes one quotient
 estimate q = floor(v_3 / r_3) <= 5 and one conditional add-back, so the sets below cover every
 q = 0..5 and both signs of the estimate's error: k r - 1, k r, k r + 1 for k = 1..5, 2^256 - 1,
 the stems straddling the top-limb boundary of each k r, and random stems >= r. The leaf unit is

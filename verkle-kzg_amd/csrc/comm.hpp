@@ -31,7 +31,7 @@ struct Multi {
     std::function<void(const std::function<void(int)>&)> run;
 };
 
-// Node::gen_commitment level by level (verkle.cpp); sh = nullptr: the whole tree on this ctx, or
+// Node::gen_commitment level by level (verkle_commit_host.cpp); sh = nullptr: the whole tree on this ctx, or
 // with mu every level's commits cut into member slices committed concurrently (no exchange: the
 // members write into the one tree's level records directly)
 int verkle_commitment(vc_ctx* ctx, int table, vc_verkle* t, uint64_t* out_xy, uint8_t* out_inf, const Shard* sh,
@@ -48,7 +48,7 @@ void kzg_share_free(KzgShare* s);
 int kzg_share_sum(int curve, const uint64_t* parts, int G, uint64_t* total);
 int verkle_pull_host(vc_verkle* t);
 int verkle_debug_ext_stage(vc_verkle* t, int reps, double* us);
-// one context, every level device-resident (verkle.cpp; vc_verkle_commitment's default)
+// one context, every level device-resident (verkle_commit_dev.hip; vc_verkle_commitment's default)
 int verkle_commitment_dev(vc_ctx* ctx, int table, vc_verkle* t, uint64_t* out_xy, uint8_t* out_inf);
 
 }  // namespace vk

@@ -395,7 +395,7 @@ int msm_batch_sparse_items_guarded(vc_ctx* ctx, int table, size_t batch, const u
                                    const uint64_t* scalars, uint64_t* out_xy, uint8_t* out_inf, uint64_t* out_items);
 // the same on the device (BN254): CSR columns / canonical scalars already in device memory, the row
 // structure row_ptr on the host (rows_fit: every row has 1..4 non-zeros -- the chunks are the rows);
-// affine rows, flags and items written to device memory, enqueued on ctx->stream (verkle.cpp's
+// affine rows, flags and items written to device memory, enqueued on ctx->stream (verkle_commit_dev.hip's
 // device-resident levels)
 // the sparse commits' latency path (sparse_commit.hip k_fb_sparse_small, BN254): rows of (column, scalar)
 // non-zeros; mode 0: d_vals (4 canonical words per non-zero), 1: d_vals of 2 words (16-byte

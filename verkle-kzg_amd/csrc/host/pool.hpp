@@ -110,8 +110,7 @@ using uvec = std::vector<T, default_init_alloc<T>>;
 
 // fn(i) for i in [lo, hi) on the pool in contiguous ranges, or serially below `min_par` items
 template <class Fn>
-inline void pool_for(size_t lo, size_t hi, size_t min_par, Fn&& fn) {
-    HostPool& P = host_pool();
+inline void pool_for(HostPool& P, size_t lo, size_t hi, size_t min_par, Fn&& fn) {
     const size_t count = hi - lo;
     if (count < min_par || P.size() == 1) {
         for (size_t i = lo; i < hi; i++) fn(i);
@@ -121,6 +120,10 @@ inline void pool_for(size_t lo, size_t hi, size_t min_par, Fn&& fn) {
     P.run([&](unsigned k) {
         for (size_t i = lo + count * k / T; i < lo + count * (k + 1) / T; i++) fn(i);
     });
+}
+template <class Fn>
+inline void pool_for(size_t lo, size_t hi, size_t min_par, Fn&& fn) {
+    pool_for(host_pool(), lo, hi, min_par, fn);
 }
 
 }  // namespace vk

@@ -66,7 +66,7 @@ int kzg_open_bn254(vc_ctx* ctx, Table* t, size_t size, const uint64_t* evals, co
                    uint64_t* proof_xy, uint8_t* proof_inf, uint64_t* y);
 
 // A multiproof whose evaluation rows are sparse and already (mostly) on the device -- the verkle
-// tree proofs (verkle.cpp): the per-point sums S[row(z_i)][k] += r^i f_i[k] are accumulated from the
+// tree proofs (verkle_proof.hip): the per-point sums S[row(z_i)][k] += r^i f_i[k] are accumulated from the
 // rows' non-zeros instead of Q x N dense evaluations. The n_rows distinct rows are given in CSR
 // form: row d's non-zeros are [row_ptr[d], row_ptr[d + 1]) of col / src, columns strictly ascending;
 // src s means the canonical Fr value d_item[4 s] (s < n_item; device memory) or, with MP_SRC_AUX
