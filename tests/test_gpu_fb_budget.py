@@ -1,4 +1,4 @@
-"""Fixed-base tables built on first use (csrc/commit.hip fb_default_c): the widest window <= 16
+"""Fixed-base tables built on first use (csrc/commit_internal.hpp fb_default_c): the widest window <= 16
 bits that fits what is left of the context's budget for such tables (VKZG_FB_BUDGET_GB, default
 20 GB) -- 16 bits (17.2 GB) for the first 257-point table of a context, narrower ones after it --
 and the same commitments whatever window a table got."""

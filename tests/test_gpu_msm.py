@@ -302,6 +302,32 @@ def test_batch_commit_mixed_windows(engines, oracle_c, curve, c, windows):
         e.fixed_base_precompute(tid, 8, 10)
 
 
+@pytest.mark.parametrize("curve", CURVES)
+@pytest.mark.parametrize("batch", [257, 513])
+def test_batch_commit_norm_block_edges(engines, oracle_c, curve, batch):
+    """The split normalisation's 256-element blocks (normalize.hip k_norm_prep / k_norm_finish) at
+    their edges: width-3 commits above the latency path's 64, 257 (a block with a single live lane)
+    and 513, all-zero scalars (the identity: denominator 1 on the SW curves) for commits 0, 255, 256
+    and batch - 1; every commit against the oracle."""
+    import vkzg
+    e = engines[curve]
+    rng = np.random.default_rng(257)
+    width = 3
+    tid = e.random_bases(width, seed=11)
+    xy, inf = e.download_bases(tid)
+    e.fixed_base_precompute(tid, 8)
+    sc = vkzg.random_scalars(curve, width * batch, rng)
+    for j in (0, 255, 256, batch - 1):
+        sc[j * width:(j + 1) * width] = 0
+    got_xy, got_inf = e.msm_batch(tid, sc, width)
+    for j in range(batch):
+        want = _oracle(oracle_c, curve, xy, inf, sc[j * width:(j + 1) * width], threads=1)
+        assert got_inf[j] == want[1], j
+        assert bool(want[1]) == (j in (0, 255, 256, batch - 1)), j
+        if not want[1]:
+            assert np.array_equal(got_xy[j], want[0]), j
+
+
 def test_batch_commit_edwards_identity(engines, oracle_c):
     """Bandersnatch commits that sum to the identity through P + (-P) (Edwards identity (0 : Z : Z)
     with Z != 1): the device normalisation (large batches, k_norm_prep / k_norm_finish) must divide
@@ -320,13 +346,15 @@ def test_batch_commit_edwards_identity(engines, oracle_c):
     e.fixed_base_precompute(tid, 8)
     rng = np.random.default_rng(8)
     ident_xy = np.array([0, 0, 0, 0, 1, 0, 0, 0], dtype=np.uint64)
-    for batch in (3, 100):                               # host latency path, device normalisation
+    # host latency path, device normalisation (every other commit the identity), and 257 commits with
+    # the identities at 255 and 256: the last of a full block, and the lone member of the next one
+    for batch, idents in ((3, range(0, 3, 2)), (100, range(0, 100, 2)), (257, (255, 256))):
         sc = vkzg.random_scalars("bandersnatch", 2 * batch, rng)
-        for j in range(0, batch, 2):
+        for j in idents:
             sc[2 * j + 1] = sc[2 * j]                    # a P + a (-P) = O
         got_xy, got_inf = e.msm_batch(tid, sc, 2)
         for j in range(batch):
-            if j % 2 == 0:
+            if j in idents:
                 assert got_inf[j] == 1 and np.array_equal(np.asarray(got_xy[j], dtype=np.uint64), ident_xy), (batch, j)
             else:
                 want = _oracle(oracle_c, "bandersnatch", xy, inf, sc[2 * j:2 * j + 2])

@@ -231,7 +231,7 @@ def test_verkle_mirror_moves_between_devices(oracle_c):
 
 @pytest.mark.parametrize("mode", ["late", "selfinv", "unfused", "nolead"])
 def test_verkle_norm_finish_modes(eng, mode, monkeypatch):
-    """The verkle levels' normalisation (commit.hip normalize_rows_items): by default the finish
+    """The verkle levels' normalisation (normalize.hip normalize_rows_items): by default the finish
     kernel is queued behind the prep before the host has inverted the block products, its blocks
     waiting on the host's go word. == the finish launched after the inversion (late,
     VKZG_NORM_EARLY=0) and == blocks that stop waiting after 1 us and invert on their own

@@ -1,6 +1,7 @@
 // Engine context: one device, one stream, base tables, grow-only workspaces, kernel timers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <immintrin.h>
 
 #include <chrono>
 #include <cstdlib>
@@ -108,7 +109,7 @@ struct PinBuf {
     PinBuf& operator=(const PinBuf&) = delete;
 };
 
-// window schedule of a fixed-base table (commit.hip): W signed-digit windows, the last `big` of
+// window schedule of a fixed-base table (fb_table.hip): W signed-digit windows, the last `big` of
 // them c + 1 bits wide and the rest c, so a scalar of B bits needs c W + big >= B + 1. Base i's
 // block holds stride() entries; window w's 2^(width(w) - 1) multiples start at off(w). Mixed
 // widths put a table between two uniform sizes: Bandersnatch c = 18, W = 14, big = 2 is 58 GB
@@ -146,7 +147,7 @@ struct Table {
     int win_pair = 0;   // radix copies in the pair layout (SW29::AffP, one 128-B record per signed copy)
     DevBuf win;
     // the first few bases as a table of their own with wider fixed-base windows (lead_table in
-    // commit.hip: the verkle extension rows [1, stem, c1, c2] use bases 0..3 only); owned, built on
+    // fb_table.hip: the verkle extension rows [1, stem, c1, c2] use bases 0..3 only); owned, built on
     // first use, dropped when the bases are refilled
     Table* lead = nullptr;
     int lead_k = 0, lead_c = 0;
@@ -284,7 +285,7 @@ struct vc_ctx {
     void timer_end(const char* name, hipEvent_t a, hipStream_t s = nullptr);
     void collect_timers();  // call after the stream is synchronised
     vk::Lane lane(int i) { return i == 0 ? vk::Lane{stream, ws, &pin[0]} : vk::Lane{side_stream, ws2, &pin[1]}; }
-    // bytes of the fixed-base tables built on first use that this context still holds (commit.hip
+    // bytes of the fixed-base tables built on first use that this context still holds (commit_internal.hpp
     // fb_default_c's budget; a table refilled or re-precomputed explicitly stops counting)
     size_t fb_auto_used() const {
         size_t s = 0;
@@ -353,6 +354,26 @@ inline bool verkle_stamps() {
 inline double clock_us() {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+// The bounded host poll of completion flags in page-locked memory: spins on seen() until it holds
+// (true) or, the clock looked at every 1,024 spins, 20 ms have passed (false: a first launch
+// loading its code, or a fault -- the caller then waits for the stream, which also reports any
+// error). The acquire fence after a flag is the caller's.
+template <class Pred>
+inline bool poll_bounded(Pred&& seen) {
+    const auto w0 = std::chrono::steady_clock::now();
+    for (uint32_t spins = 0;; spins++) {
+        if (seen()) return true;
+        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - w0 > std::chrono::milliseconds(20)) return false;
+        _mm_pause();
+    }
+}
+// the next completion-flag epoch of a counter, never 0 (what cleared flags hold)
+inline uint32_t next_epoch(uint32_t& counter) {
+    if (++counter == 0) ++counter;
+    return counter;
+}
+inline uint32_t next_epoch(vc_ctx* ctx) { return next_epoch(ctx->small_epoch); }
 
 // implemented per translation unit with explicit instantiations
 int device_mad_rate(vc_ctx* ctx, double* tera_per_s);
@@ -426,7 +447,7 @@ int sparse_small_items_dev(vc_ctx* ctx, Table* t, const SmallRows& in,
                            const std::function<void()>* overlap = nullptr);
 size_t sparse_small_pairs(const Table* t, size_t nnz);  // (non-zero, window) pairs of nnz non-zeros
 // BN254 rows -> (optional old-commitment adds) canonical affine points, flags, to_data_item at
-// dst[j] (commit.hip); no final sync
+// dst[j] (normalize.hip); no final sync
 int normalize_rows_items(vc_ctx* ctx, void* d_rows, size_t n, const uint32_t* add_ids, const uint64_t* add_xy,
                          const uint8_t* add_inf, const uint32_t* dst, uint64_t* out_xy, uint8_t* out_inf,
                          uint64_t* out_item, const std::function<void()>* overlap = nullptr);

@@ -57,7 +57,7 @@ struct SW29 {
         a.y = unpack29<P>(p->y.v);
         return a;
     }
-    // a table point already in limbs (fixed-base tables, commit.hip FbE)
+    // a table point already in limbs (fixed-base tables, fb_table.hip FbE)
     VK_HD static Aff load(const Aff* p) { return *p; }
     VK_HD static Acc dbl_aff(const f29<P>& x, const f29<P>& y) {
         const f29<P> U = add29<P>(y, y);
@@ -371,7 +371,7 @@ struct Fast29<Bandersnatch> {
     using type = TE29<Bandersnatch, F29BLS381Fr>;
 };
 
-// Fixed-base window table entry (commit.hip; read by the sparse commits' accumulate, msm.hip).
+// Fixed-base window table entry (fb_table.hip; read by the sparse commits' accumulate, msm.hip).
 // Table entry (kept as a type so the layout can change in one place): the radix-2^29 limbs the
 // mixed add consumes (ec29.hpp Aff, 4 B per 29-bit limb: 108 B for Bandersnatch's x, y, d x y),
 // so the loop reads operands with no unpacking (~53 of 2,250 instructions per Edwards add).

@@ -4,7 +4,7 @@
 // round). Here the folded generator g^(k)_j is kept as scalar coefficients over the ORIGINAL
 // CRS (coeff_i, the prover-side twin of the verifier's points_coeffs), so each round's
 // L and R are two width-(N+1) fixed-base commitments (q is base N) served by the
-// precomputed window tables of commit.hip. Same group elements, no point folding.
+// precomputed window tables of fb_table.hip. Same group elements, no point folding.
 #include "ipa_rounds.hpp"
 #include "protocol.hpp"
 

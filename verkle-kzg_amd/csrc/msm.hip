@@ -16,7 +16,6 @@
 // thread is fixed (M entries) even when every scalar hits one bucket.
 // Here: the slices and the msm_run* paths; their geometry is msm_plan.hpp's, the tables msm_tables.hip's.
 #include <hip/hip_runtime.h>
-#include <immintrin.h>
 
 #include <algorithm>
 #include <atomic>
@@ -189,7 +188,7 @@ static int slice_enqueue(vc_ctx* ctx, MsmSlice<C>& sl, Src src, size_t nv, const
         // (fresh page-locked memory holds anything: no stale flag may match)
         volatile uint32_t* hf = reinterpret_cast<volatile uint32_t*>(static_cast<uint8_t*>(L.pin->p) + sl.flag_off);
         for (uint32_t k = 0; k < sl.nflags; k++) hf[k] = 0;
-        sl.epoch = ++ctx->tail_epoch == 0 ? ++ctx->tail_epoch : ctx->tail_epoch;  // never 0
+        sl.epoch = next_epoch(ctx->tail_epoch);
         uint8_t* dbase = static_cast<uint8_t*>(L.pin->dp);
         td.flags = reinterpret_cast<uint32_t*>(dbase + sl.flag_off);
         td.epoch = sl.epoch;
@@ -220,16 +219,14 @@ static int slice_wait(const MsmSlice<C>& sl) {
     if (sl.direct) {
         const volatile uint32_t* hf =
             reinterpret_cast<const volatile uint32_t*>(static_cast<const uint8_t*>(sl.L.pin->p) + sl.flag_off);
-        const auto w0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 0;; spins++) {
+        const bool seen = poll_bounded([&] {
             uint32_t k = 0;
             while (k < sl.nflags && hf[k] == sl.epoch) k++;
-            if (k == sl.nflags) {
-                std::atomic_thread_fence(std::memory_order_acquire);
-                return VC_OK;
-            }
-            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - w0 > std::chrono::milliseconds(20)) break;
-            _mm_pause();
+            return k == sl.nflags;
+        });
+        if (seen) {
+            std::atomic_thread_fence(std::memory_order_acquire);
+            return VC_OK;
         }
     }
     VK_CHECK_HIP(hipStreamSynchronize(sl.L.st));

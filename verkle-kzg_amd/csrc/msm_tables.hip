@@ -201,7 +201,7 @@ int win_tables(vc_ctx* ctx, Table* t, int c, int W, int ts, uint32_t mul, bool p
     // (168 B) so the accumulate never negates
     t->win_pair = pair ? 1 : 0;
     VK_TRY(t->win.ensure((size_t)W * 2 * n * (pair ? 2 * sizeof(FP) : sizeof(FA))));
-    Table cur;  // 2^(c w) P (affine, Montgomery): normalised by table_from_acc (commit.hip)
+    Table cur;  // 2^(c w) P (affine, Montgomery): normalised by table_from_acc (fb_table.hip)
     DevBuf nxt, acc;
     VK_TRY(nxt.ensure(n * sizeof(Aff)));
     VK_TRY(acc.ensure(n * sizeof(Acc)));

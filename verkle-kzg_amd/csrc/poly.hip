@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "batch_inv.hpp"
 #include "ctx.hpp"
 #include "ec.hpp"
 #include "poly.hpp"
@@ -50,7 +51,7 @@ __global__ void k_powers(fe<F> w, size_t n, fe<F>* __restrict__ out) {
 // LDS) and inverts their product, then every chunk's inverse is
 // inv(total) * prefix * suffix and the chunk is substituted backwards. One inversion per 256 CH
 // elements (per chunk before: 65,536 inversions for a 2^20 KZG quotient, 0.46 ms).
-// The workgroup products are inverted on the host (as commit.hip's split normalisation): a
+// The workgroup products are inverted on the host (as normalize.hip's split normalisation): a
 // per-workgroup lane inversion was ~130 us of serial binary Euclid on one GPU lane, the host
 // inverts all workgroup products with one inversion in a few us. k_binv_prep leaves the chunk
 // prefix products in out[], each chunk the product of its workgroup's OTHER chunk products, and
@@ -69,22 +70,8 @@ __global__ void __launch_bounds__(256) k_binv_prep(const fe<F>* __restrict__ in,
         if (!fe_is_zero<F>(v)) acc = fe_mul<F>(acc, v);
         out[k] = acc;  // chunk prefix products
     }
-    pre[t] = acc;
-    suf[t] = acc;
-    __syncthreads();
-    for (uint32_t off = 1; off < 256; off <<= 1) {
-        fe<F> p = pre[t], q = suf[t];
-        if (t >= off) p = fe_mul<F>(pre[t - off], p);
-        if (t + off < 256) q = fe_mul<F>(q, suf[t + off]);
-        __syncthreads();
-        pre[t] = p;
-        suf[t] = q;
-        __syncthreads();
-    }
-    fe<F> o = fe_one<F>();
-    if (t > 0) o = pre[t - 1];
-    if (t < 255) o = t > 0 ? fe_mul<F>(o, suf[t + 1]) : suf[t + 1];
-    others[c] = o;
+    block_scan256<F>(acc, pre, suf);
+    others[c] = scan_others<F>(pre, suf);
     if (t == 0) tot[blockIdx.x] = pre[255];
 }
 
@@ -276,17 +263,10 @@ int batch_inverse(vc_ctx* ctx, const fe<F>* d_in, fe<F>* d_out, size_t n) {
               tot.as<fe<F>>());
     VK_CHECK_HIP(hipMemcpyAsync(h, tot.p, nblk * sizeof(fe<F>), hipMemcpyDeviceToHost, ctx->stream));
     VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    fe<F>* inv = h + nblk;  // Montgomery's trick over the workgroup products (never zero)
-    inv[0] = h[0];
-    for (size_t b = 1; b < nblk; b++) inv[b] = fe_mul<F>(inv[b - 1], h[b]);
-    fe<F> run = fe_inv_bin<F>(inv[nblk - 1]);
-    for (size_t b = nblk - 1; b > 0; b--) {
-        const fe<F> ib = fe_mul<F>(run, inv[b - 1]);
-        run = fe_mul<F>(run, h[b]);
-        inv[b] = ib;
-    }
-    inv[0] = run;
-    VK_CHECK_HIP(hipMemcpyAsync(tot.p, inv, nblk * sizeof(fe<F>), hipMemcpyHostToDevice, ctx->stream));
+    BlockInverses<F> bi{h, h + nblk, nblk};  // Montgomery's trick over the workgroup products (never zero)
+    bi.take(nblk);
+    bi.finish();
+    VK_CHECK_HIP(hipMemcpyAsync(tot.p, bi.inv, nblk * sizeof(fe<F>), hipMemcpyHostToDevice, ctx->stream));
     VK_LAUNCH(ctx, "binv_finish", (k_binv_finish<F>), nblk, 256, 0, d_in, d_out, n, CH, others.as<fe<F>>(),
               tot.as<fe<F>>());
     VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // the pinned inverses are reused by the next call

@@ -387,7 +387,7 @@ static int sparse_commit_dev(vc_ctx* ctx, Table* t, size_t batch, const uint64_t
     const char* fe_env = getenv("VKZG_SPARSE_FUSED");
     const bool fused = !(fe_env && atoi(fe_env) == 0);
     if (fused) {
-        // the arrival counter: a word of the normalisation's zeroed counter buffer (commit.hip)
+        // the arrival counter: a word of the normalisation's zeroed counter buffer (normalize.hip)
         DevBuf& cntb = ctx->ws[WS_NORM_CNT];
         if (cntb.p == nullptr) {
             VK_TRY(cntb.ensure(256));
@@ -397,7 +397,7 @@ static int sparse_commit_dev(vc_ctx* ctx, Table* t, size_t batch, const uint64_t
         VK_TRY(d_eoff.ensure(nb * 8 + (nb + 1) * 4));
         uint64_t* bsum = d_eoff.as<uint64_t>();
         uint32_t* boff = reinterpret_cast<uint32_t*>(bsum + nb);
-        const uint32_t epoch = ++ctx->small_epoch == 0 ? ++ctx->small_epoch : ctx->small_epoch;  // never 0
+        const uint32_t epoch = next_epoch(ctx);
         VK_LAUNCH(ctx, "sparse_count_scan", (k_sparse_count_scan<Fr>), (unsigned)nb, 256, 0, d_sc, nnz, mont, fg,
                   d_cnt.as<uint32_t>(), bsum, boff, cntb.as<uint32_t>() + 16, Tmax > 0 ? chain_max : (uint32_t*)nullptr,
                   epoch);

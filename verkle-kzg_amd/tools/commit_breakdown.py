@@ -1,6 +1,6 @@
 """C3 probe: per-kernel times of one 10k x width-256 Bandersnatch batched commit (fixed-base
 table at window c, or "c:W" for W mixed windows of c / c + 1 bits): fb_commit (chunk-major main
-kernel), fb_combine, fb_normalize_out."""
+kernel), fb_combine, norm_prep, norm_finish."""
 import os
 import sys
 import time
@@ -40,7 +40,7 @@ for arg in sys.argv[1:] or ["16"]:
     for _ in range(reps):
         e.msm_batch_device(tab, 256, dcs.data_ptr(), B, dxy.data_ptr(), dinf.data_ptr())
     torch.cuda.synchronize()
-    ks = {k: e.kernel_time(k) for k in ("fb_commit", "fb_combine", "fb_normalize_out", "norm_prep", "norm_finish")}
+    ks = {k: e.kernel_time(k) for k in ("fb_commit", "fb_combine", "norm_prep", "norm_finish")}
     e.enable_timing(False)
     print(f"c={c} B={B}: wall {wall:.3f} ms/batch ({B / wall * 1e3 / 1e6:.3f} M commits/s); " +
           ", ".join(f"{k} {ms / n:.3f} ms" for k, (ms, n) in ks.items() if n), flush=True)

@@ -54,7 +54,7 @@ for it in range(3):
 e.enable_timing(True)
 e.reset_timing()
 ipa.prove_point(c, 1000, d)
-for k in ("fb_commit_small", "fb_combine_small", "fb_normalize_out", "fb_commit", "fb_combine"):
+for k in ("fb_commit_small", "fb_commit", "fb_combine"):
     ms, n = e.kernel_time(k)
     if n:
         print(f"  {k}: {n} launches, {ms / n * 1e3:.1f} us avg", flush=True)
