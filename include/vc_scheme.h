@@ -195,8 +195,13 @@ int vc_ipa_verify_commitment_proof(vc_ctx* ctx, int table, const uint64_t* com_x
 /* ---------------------------------------------------------------- KZG (kzg/mod.rs)
  * prove_point (:136-154): y = evaluate(point), q = divide_by_vanishing(index) when
  * point <= size, else divide_by_vanishing_outside_domain(point); proof = MSM(L, q).
- * evals may be shorter than the domain (`max`); VC_E_DOMAIN for point == size (the
- * reference panics there, Appendix B.4). */
+ * evals may be shorter than the domain (`max`). The point's status is decided on the host
+ * before any GPU work and a failing call leaves the outputs untouched: VC_E_INVALID for a
+ * point >= r, VC_E_DOMAIN for point == size (the reference panics there, Appendix B.4) and
+ * for a domain element that is not below size (z^size == 1, r - 1 = w^(size / 2) among them:
+ * the reference divides by zero, precompute.rs:86), VC_OK otherwise. The same holds for
+ * the device, part and commit+prove forms below, for vc_kzg_quotient and for
+ * vc_group_kzg_prove (every member fails alike: no partial result). */
 int vc_kzg_prove(vc_ctx* ctx, int table, size_t size, const uint64_t* evals, size_t max,
                  const uint64_t* point, uint64_t* proof_xy, uint8_t* proof_inf, uint64_t* y);
 /* same with the evaluations already in device memory (canonical, 4 u64 each) */

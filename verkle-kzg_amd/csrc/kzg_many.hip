@@ -127,15 +127,10 @@ int prove_many_t(vc_ctx* ctx, Table* t, const Args& a) {
     std::vector<uint8_t> outside(n);
     std::atomic<int> bad{0};  // 1: a point >= r; 2: a domain error
     pool_for(0, n, 1024, [&](size_t i) {
-        const uint32_t* zw = pts32 + (size_t)F::N * i;
-        if (!words_canonical<F>(zw)) {
-            bad |= 1;
-            return;
-        }
-        const uint32_t c = classify<F>(zw, (uint32_t)N);
-        outside[i] = c == KM_OUTSIDE;
-        if (c == KM_AT_N) bad |= 2;
-        if (c == KM_OUTSIDE && fe_is_zero<F>(vanishing<F>(fe_to_mont<F>(words_load<F>(zw)), lgN))) bad |= 2;
+        uint32_t c = 0;
+        const int st = point_status<F>(pts32 + (size_t)F::N * i, (uint32_t)N, lgN, &c);
+        if (st == VC_OK) outside[i] = c == KM_OUTSIDE;
+        else bad |= st == VC_E_INVALID ? 1 : 2;
     });
     if (bad & 1) return VC_E_INVALID;
     if (bad & 2) return VC_E_DOMAIN;

@@ -26,44 +26,12 @@
 //   q_i = (f_i - y) / (w^i - z)
 #pragma once
 #include "ff.hpp"
+#include "kzg_point.hpp"  // the point's class, z^N - 1 and the status rules, shared with the single open
 
 namespace vk {
 namespace kzgm {
 
-constexpr uint32_t KM_OUTSIDE = 0xffffffffu;  // the point is not below or at N: the barycentric branch
-constexpr uint32_t KM_AT_N = 0xfffffffeu;     // the point equals N: the reference panics (Appendix B.4)
 constexpr uint32_t KM_MAX_N = 1024;
-
-template <class F>
-VK_HD fe<F> words_load(const uint32_t* w) {  // the words as they are (no conversion)
-    fe<F> r;
-    for (int i = 0; i < F::N; i++) r.v[i] = w[i];
-    return r;
-}
-// canonical words below the modulus
-template <class F>
-VK_HD bool words_canonical(const uint32_t* w) {
-    for (int i = F::N - 1; i >= 0; i--)
-        if (w[i] != F::p(i)) return w[i] < F::p(i);
-    return false;
-}
-
-// prove_point's branch: the canonical point as an integer. m < N: in the domain at m.
-template <class F>
-VK_HD uint32_t classify(const uint32_t* z, uint32_t N) {
-    uint32_t hi = 0;
-    for (int k = 1; k < F::N; k++) hi |= z[k];
-    if (hi != 0 || z[0] > N) return KM_OUTSIDE;
-    return z[0] == N ? KM_AT_N : z[0];
-}
-
-// D = z^N - 1, N = 2^lgN (Montgomery in and out). Zero exactly for the domain's elements.
-template <class F>
-VK_HD fe<F> vanishing(const fe<F>& z, int lgN) {
-    fe<F> p = z;
-    for (int k = 0; k < lgN; k++) p = fe_sqr<F>(p);
-    return fe_sub<F>(p, fe_one<F>());
-}
 
 template <class F>
 VK_HD fe<F> row_at(const fe<F>* f, uint32_t width, uint32_t i) {

@@ -1,9 +1,26 @@
 // KZG openings (reference: vector-commit/src/kzg/mod.rs): one point, all points (FK), the
 // range-sharded open and the SRS set-up.
+#include "kzg_point.hpp"
 #include "poly.hpp"
 #include "protocol.hpp"
 
 namespace vk {
+
+static int lg2_of(size_t n) {
+    int lg = 0;
+    while (((size_t)1 << lg) < n) lg++;
+    return lg;
+}
+
+// The status a single open takes from its point alone (kzg_point.hpp: the rules of the batch,
+// vc_kzg_prove_many), decided on the host before any GPU work so that a failing call writes no
+// output: VC_E_INVALID for a point >= r, VC_E_DOMAIN for point == size and for a domain element
+// that is not below size (z^size == 1, r - 1 among them). size: a power of two below 2^31.
+template <class Fr_>
+static int open_point_status(size_t size, const uint64_t* point) {
+    uint32_t cls = 0;
+    return kzgm::point_status<Fr_>(reinterpret_cast<const uint32_t*>(point), (uint32_t)size, lg2_of(size), &cls);
+}
 
 // ---------------------------------------------------------------- KZG (a3/a4/a5/a6/a7)
 // evals: host (d_evals == false) or device canonical scalars; out_acc != nullptr returns the
@@ -14,8 +31,9 @@ static int kzg_prove_t(vc_ctx* ctx, Table* t, size_t size, const uint64_t* evals
                        uint64_t* proof_xy, uint8_t* proof_inf, uint64_t* y_out, uint64_t* q_out, bool d_evals = false,
                        int part = 0, int parts = 1, uint32_t* out_acc = nullptr, uint64_t* com_xy = nullptr,
                        uint8_t* com_inf = nullptr) {
-    if (!is_pow2(size) || max > size) return VC_E_INVALID;
+    if (!is_pow2(size) || (size >> 31) || max > size) return VC_E_INVALID;
     if (t && t->n < size) return VC_E_RANGE;
+    VK_TRY(open_point_status<Fr_>(size, point));
     DevBuf d_f(ctx), d_q(ctx), pw(ctx), tmp(ctx), part_buf(ctx);
     VK_TRY(d_f.ensure(size * 32));
     VK_TRY(d_q.ensure(size * 32));
@@ -154,11 +172,6 @@ __global__ void k_pt_gather(const typename C::Acc* __restrict__ src, uint32_t n,
     if (i < n) out[i] = i < valid ? src[base + dir * (int64_t)i] : C::zero();
 }
 
-static int lg2_of(size_t n) {
-    int lg = 0;
-    while (((size_t)1 << lg) < n) lg++;
-    return lg;
-}
 // in-place FFT (inverse: iFFT incl. the 1/n) of n = 2^k points / field elements in a DevBuf
 template <class C, class Fr_>
 static int pt_fft(vc_ctx* ctx, DevBuf& a, size_t n, bool inverse) {
@@ -462,8 +475,9 @@ template <class C_, class Fr_>
 static int kzg_share_begin_t(vc_ctx* ctx, Table* t, size_t size, const uint64_t* evals, size_t max,
                              const uint64_t* point, size_t lo, size_t hi, KzgShare* s, uint64_t* partial) {
     using Fe = fe<Fr_>;
-    if (!is_pow2(size) || max > size || lo > hi || hi > size) return VC_E_INVALID;
+    if (!is_pow2(size) || (size >> 31) || max > size || lo > hi || hi > size) return VC_E_INVALID;
     if (t->n < size) return VC_E_RANGE;
+    VK_TRY(open_point_status<Fr_>(size, point));  // every member sees the same point: all fail alike
     s->ctx = ctx;
     s->t = t;
     s->n = size;
@@ -493,7 +507,8 @@ static int kzg_share_begin_t(vc_ctx* ctx, Table* t, size_t size, const uint64_t*
     VK_TRY(s->inv.ensure(L * 32));
     if (s->nvalid)
         VK_CHECK_HIP(hipMemcpyAsync(s->q.p, evals + 4 * lo, s->nvalid * 32, hipMemcpyHostToDevice, ctx->stream));
-    VK_TRY(canon_to_mont_dev<Fr_>(ctx, s->q.p, s->L, s->nvalid, s->f.as<Fe>()));
+    // (an empty share, size < G, has nothing to convert: no launch with a grid of zero blocks)
+    if (s->L) VK_TRY(canon_to_mont_dev<Fr_>(ctx, s->q.p, s->L, s->nvalid, s->f.as<Fe>()));
     Fe part;
     VK_TRY(kzg_range_part<Fr_>(ctx, size, s->f.as<Fe>(), s->nvalid, lo, s->L, pm, omega, s->in_domain, s->m, fm,
                                s->q.as<Fe>(), s->inv.as<Fe>(), s->part, &part));

@@ -463,7 +463,9 @@ int kzg_range_part(vc_ctx* ctx, size_t n, const fe<F>* d_f, size_t nvalid, size_
         VK_LAUNCH(ctx, "kzg_q_in", (k_q_in_range<F>), nblk, 256, 0, d_f, nvalid, inv1, pwp, n, lo, L, m, wminv, fm,
                   d_q, part.as<fe<F>>());
     } else {
-        VK_LAUNCH(ctx, "kzg_den", (k_den<F>), (L + 255) / 256, 256, 0, pwp + lo, L, point, (long long)-1, d_q);
+        // (an empty share launches neither: a grid of zero blocks is an error to the runtime; the one
+        // block of the sum below then leaves a zero partial)
+        if (L) VK_LAUNCH(ctx, "kzg_den", (k_den<F>), (L + 255) / 256, 256, 0, pwp + lo, L, point, (long long)-1, d_q);
         VK_TRY(batch_inverse<F>(ctx, d_q, d_inv, L));
         VK_LAUNCH(ctx, "kzg_bary", (k_bary_partial<F>), nblk, 256, 0, d_f, nvalid, pwp + lo, d_inv, L, part.as<fe<F>>());
     }

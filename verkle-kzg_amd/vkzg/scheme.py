@@ -771,6 +771,10 @@ class KZG:
         return _pt(xy, inf)
 
     def prove_point(self, commitment, point, data, transcript=None):
+        """one opening (vc_kzg_prove) -> {"proof", "y"}; the point is taken mod r. VCError with
+        status VC_E_DOMAIN (-8) where the reference panics: point == size, and a domain element that
+        is not below size (z^size == 1, r - 1 among them). (The C call also returns VC_E_INVALID for
+        a point >= r; the reduction here keeps that from happening.) A failing call proves nothing."""
         ev = data.limbs()
         pxy = np.zeros(2 * self.nl, dtype=np.uint64)
         pinf = np.zeros(1, dtype=np.uint8)
