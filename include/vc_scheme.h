@@ -421,6 +421,47 @@ int vc_multiproof_verify_kzg(vc_ctx* ctx, const vc_kzg_vk* vk, size_t N, size_t 
                              uint8_t d_inf, const uint64_t* kzg_proof_xy, uint8_t kzg_proof_inf,
                              const uint64_t* kzg_y, int* result);
 
+/* ---- P multiproofs in one call, one verdict each (csrc/mp_verify.hip): the transcripts, the
+ * coefficients r^i / (t - z_i), the sums E_p, the claims E_p - D_p and the inner verification all
+ * run on the device, per chunk of at most 8,192 proofs and 2^18 queries (the workspace does not
+ * grow with P); nothing of a proof crosses to the host before the verdicts (or claims) come back.
+ * Layout: proof p owns queries [q_ptr[p], q_ptr[p + 1]) of the flat query arrays (q_ptr: P + 1
+ * ascending offsets; com_xy total x 8, com_inf total, z total, y total x 4 u64); q_ptr == NULL: every
+ * proof has Q queries, vc_multiproof_prove_many's [P][Q] layout (Q is not read otherwise). d_xy
+ * P x 8, d_inf P. The inner IPA proofs in vc_ipa_verify_many's flat layout (l_xy / r_xy P x K x 8,
+ * l_inf / r_inf P x K, tip and ipa_y P x 4, K = log2 N), the inner KZG proofs in
+ * vc_kzg_verify_many's (kzg_xy P x 8, kzg_inf P, kzg_y P x 4). All values canonical.
+ * results[p] is what vc_multiproof_verify_ipa / _kzg gives for proof p wherever that call returns
+ * VC_OK. Malformed proof content gives the verdict 0 with VC_OK, as in the other _many verifiers:
+ * a coordinate of a C_i, of D or of an inner point >= p, such a point off the curve, a y_i, tip or
+ * inner y >= r. No entry changes another's verdict; the identity flag is a valid point.
+ * vc_multiproof_claims_many reports such an entry in malformed[p] (its outputs unspecified) and
+ * otherwise gives vc_multiproof_kzg_claim's (E - D, t) bit for bit (c_xy P x 8, zero for the
+ * identity, c_inf P, t P x 4). The coefficients are mp_claim's: the denominator is t - z_i with z_i
+ * the integer. A t that is itself an integer below N (no test can produce one: it is a hash) gives
+ * the entry the verdict 0 / malformed 1.
+ * Statuses, decided on the host before any GPU work with nothing written: VC_E_INVALID for N not a
+ * power of two in [2, 2^28] (the inner many-verifiers' bound), a context or key that is not BN254,
+ * a null array with P > 0, a q_ptr that is not ascending, a proof with 0 or more than VC_MPV_Q_MAX
+ * queries (long proofs stay with the single call, where the host's SHA-256 beats one lane's), for
+ * IPA a table with fewer than N + 1 points; VC_E_TABLE for an unknown table; then VC_E_DOMAIN for
+ * the whole call when any z_i >= N (the verifier's own input, as in the single call). P = 0 is
+ * VC_OK. */
+#define VC_MPV_Q_MAX 4096
+int vc_multiproof_claims_many(vc_ctx* ctx, size_t N, size_t P, const uint64_t* q_ptr, size_t Q,
+                              const uint64_t* com_xy, const uint8_t* com_inf, const uint64_t* z, const uint64_t* y,
+                              const uint64_t* d_xy, const uint8_t* d_inf, uint64_t* c_xy, uint8_t* c_inf, uint64_t* t,
+                              uint8_t* malformed);
+int vc_multiproof_verify_many_ipa(vc_ctx* ctx, int table, size_t N, size_t P, const uint64_t* q_ptr, size_t Q,
+                                  const uint64_t* com_xy, const uint8_t* com_inf, const uint64_t* z,
+                                  const uint64_t* y, const uint64_t* d_xy, const uint8_t* d_inf, const uint64_t* l_xy,
+                                  const uint8_t* l_inf, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* tip,
+                                  const uint64_t* ipa_y, uint8_t* results);
+int vc_multiproof_verify_many_kzg(vc_ctx* ctx, const vc_kzg_vk* vk, size_t N, size_t P, const uint64_t* q_ptr,
+                                  size_t Q, const uint64_t* com_xy, const uint8_t* com_inf, const uint64_t* z,
+                                  const uint64_t* y, const uint64_t* d_xy, const uint8_t* d_inf, const uint64_t* kzg_xy,
+                                  const uint8_t* kzg_inf, const uint64_t* kzg_y, uint8_t* results);
+
 /* ---------------------------------------------------------------- KZG verification on BLS12-381
  * A verifying key has a curve: VC_CURVE_BN254 (every call above that takes no curve argument, as
  * before) or VC_CURVE_BLS12_381 (csrc/pairing_bls.hpp: the ate pairing over the 64 bits of

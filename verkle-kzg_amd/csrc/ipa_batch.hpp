@@ -86,8 +86,21 @@ VK_HD void put_tail(uint32_t* m, int off, int len, int blocks) {
     m[16 * blocks - 1] = (uint32_t)len * 8;
 }
 
+// the 48 output bytes b1 | b2[0..16) of expand_message_xmd, big-endian, mod r (Montgomery): lo +
+// hi 2^256, lo the low 32 bytes, hi the top 16 (shared with mp_verify.hpp's "multiproof" DST)
+VK_HD FrE xmd_reduce(const uint32_t b1[8], const uint32_t b2[8]) {
+    // big-endian bytes b1[0..8) b2[0..4): the least significant word is b2[3]
+    FrE lo, hi = fe_zero<BN254Fr>();
+    for (int i = 0; i < 4; i++) lo.v[i] = b2[3 - i];
+    for (int i = 0; i < 4; i++) lo.v[4 + i] = b1[7 - i];
+    for (int i = 0; i < 4; i++) hi.v[i] = b1[3 - i];
+    for (int it = 0; it < 6; it++) lo = fe_reduce_once<BN254Fr>(lo);  // < 2^256 < 6r
+    // hi 2^256 in Montgomery form is hi R^2: two conversions
+    return fe_add<BN254Fr>(fe_to_mont<BN254Fr>(lo), fe_to_mont<BN254Fr>(fe_to_mont<BN254Fr>(hi)));
+}
+
 // expand_message_xmd's end from b0 = st (the hash of the padded message) to the field element
-// (Montgomery): 48 bytes big-endian mod r = lo + hi 2^256, lo the low 32 bytes, hi the top 16
+// (Montgomery)
 VK_HD FrE xmd_finish(const uint32_t b0[8]) {
     uint32_t b1[8], b2[8], m[16];
 #pragma unroll
@@ -112,14 +125,7 @@ VK_HD FrE xmd_finish(const uint32_t b0[8]) {
     m[15] = 37 * 8;
     sha_init(b2);
     sha_compress(b2, m);
-    // big-endian bytes b1[0..8) b2[0..4): the least significant word is b2[3]
-    FrE lo, hi = fe_zero<BN254Fr>();
-    for (int i = 0; i < 4; i++) lo.v[i] = b2[3 - i];
-    for (int i = 0; i < 4; i++) lo.v[4 + i] = b1[7 - i];
-    for (int i = 0; i < 4; i++) hi.v[i] = b1[3 - i];
-    for (int it = 0; it < 6; it++) lo = fe_reduce_once<BN254Fr>(lo);  // < 2^256 < 6r
-    // hi 2^256 in Montgomery form is hi R^2: two conversions
-    return fe_add<BN254Fr>(fe_to_mont<BN254Fr>(lo), fe_to_mont<BN254Fr>(fe_to_mont<BN254Fr>(hi)));
+    return xmd_reduce(b1, b2);
 }
 
 // compress_g1 (arkworks SWFlags) as eight little-endian words: x with bit 255 set when y > p - y;

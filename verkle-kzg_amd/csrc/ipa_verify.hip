@@ -28,6 +28,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <future>
+#include <memory>
+#include <new>
 #include <vector>
 
 #include "ctx.hpp"
@@ -195,6 +197,83 @@ void ipa_host_challenges(size_t lo, size_t cnt, int K, const uint64_t* com_xy, c
     });
 }
 
+// ---- the device half of a chunk, for callers whose inputs are already in device memory
+// (vc_ipa_verify_many below; the multiproof many-verifier, mp_verify.hip, whose challenges are hashed
+// on the device from its own transcript state)
+struct IpaVerifyWork {
+    DevBuf rows, vs, fixed, pw, bad;
+    size_t N = 0, chunk = 0;
+    int K = 0;
+    Fr n_inv;
+    explicit IpaVerifyWork(vc_ctx* ctx) : rows(ctx), vs(ctx), fixed(ctx), pw(ctx), bad(ctx) {}
+};
+int ipa_verify_work_new(vc_ctx* ctx, size_t N, size_t chunk, IpaVerifyWork** out) {
+    using F = BN254Fr;
+    *out = nullptr;
+    std::unique_ptr<IpaVerifyWork> w(new (std::nothrow) IpaVerifyWork(ctx));
+    if (!w) return VC_E_OOM;
+    w->N = N;
+    w->chunk = chunk;
+    while ((size_t(1) << w->K) < N) w->K++;
+    const size_t T = 1 + 2 * (size_t)w->K;
+    VK_TRY(w->rows.ensure(chunk * (N + 1) * 32));
+    VK_TRY(w->vs.ensure(chunk * T * 32));
+    VK_TRY(w->fixed.ensure(chunk * 65));  // the fixed rows' commitments and their flags
+    VK_TRY(w->bad.ensure(chunk));
+    VK_TRY(w->pw.ensure(N * 32));
+    {  // the domain's powers, once
+        std::vector<Fr> pw(N);
+        const Fr omega = bn254_group_gen(N);
+        Fr x = fe_one<F>();
+        for (size_t i = 0; i < N; i++) {
+            pw[i] = x;
+            x = fe_mul<F>(x, omega);
+        }
+        VK_CHECK_HIP(hipMemcpyAsync(w->pw.p, pw.data(), N * 32, hipMemcpyHostToDevice, ctx->stream));
+        VK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    w->n_inv = fe_inv_bin<F>(mont_from_u64<F>(N));
+    *out = w.release();
+    return VC_OK;
+}
+void ipa_verify_work_free(IpaVerifyWork* w) { delete w; }
+// cnt <= chunk proofs: field, fixed commit, curve; verdict bytes at d_out. The point arrays are
+// rewritten (k_ipa_verify_curve). laps: null, or three sums (field, fixed commit, curve, us) that
+// are added to, with a stream wait at each.
+int ipa_verify_dev(vc_ctx* ctx, Table* t, IpaVerifyWork* w, size_t cnt, const uint32_t* d_chal, const uint32_t* d_tip,
+                   const uint32_t* d_y, const uint32_t* d_point, uint32_t* d_com, const uint8_t* d_cinf, uint32_t* d_l,
+                   const uint8_t* d_linf, uint32_t* d_r, const uint8_t* d_rinf, uint8_t* d_out, double* laps) {
+    hipStream_t st = ctx->stream;
+    const size_t N = w->N;
+    uint8_t* d_fxy = w->fixed.as<uint8_t>();
+    uint8_t* d_finf = d_fxy + w->chunk * 64;
+    uint8_t* d_bad = w->bad.as<uint8_t>();
+    double c0 = 0, c1 = 0, c2 = 0;
+    if (laps) {
+        VK_CHECK_HIP(hipStreamSynchronize(st));
+        c0 = clock_us();
+    }
+    VK_LAUNCH(ctx, "ipa_verify_field", k_ipa_verify_field, cnt, 64, 0, d_chal, d_tip, d_y, d_point, w->pw.as<FrE>(),
+              w->n_inv, (uint32_t)N, w->K, w->rows.as<uint32_t>(), w->vs.as<uint32_t>(), d_bad);
+    if (laps) {
+        VK_CHECK_HIP(hipStreamSynchronize(st));
+        c1 = clock_us();
+    }
+    VK_TRY(msm_batch_run(ctx, t, N + 1, w->rows.p, cnt, /*mont=*/1, d_fxy, d_finf));
+    if (laps) {
+        VK_CHECK_HIP(hipStreamSynchronize(st));
+        c2 = clock_us();
+    }
+    VK_LAUNCH(ctx, "ipa_verify_curve", k_ipa_verify_curve, (cnt * IPA_LP + 63) / 64, 64, 0, d_com, d_cinf, d_l, d_linf,
+              d_r, d_rinf, w->vs.as<uint32_t>(), reinterpret_cast<const uint32_t*>(d_fxy), d_finf, d_bad, w->K, cnt,
+              d_out);
+    if (laps) {
+        VK_CHECK_HIP(hipStreamSynchronize(st));
+        laps[0] += c1 - c0, laps[1] += c2 - c1, laps[2] += clock_us() - c2;
+    }
+    return VC_OK;
+}
+
 }  // namespace vk
 
 using namespace vk;
@@ -237,15 +316,14 @@ extern "C" int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n, co
     chunk = std::min(chunk, n);
     const bool timing = host_timing();
 
-    DevBuf d_rows(ctx), d_vs(ctx), d_chal(ctx), d_fr(ctx), d_pts(ctx), d_flags(ctx), d_fixed(ctx), d_pw(ctx), d_res(ctx);
-    VK_TRY(d_rows.ensure(chunk * (N + 1) * 32));
-    VK_TRY(d_vs.ensure(chunk * T * 32));
+    DevBuf d_chal(ctx), d_fr(ctx), d_pts(ctx), d_flags(ctx), d_res(ctx);
+    IpaVerifyWork* work_raw = nullptr;
+    VK_TRY(ipa_verify_work_new(ctx, N, chunk, &work_raw));  // rows, scalars, fixed commitments, w^i
+    std::unique_ptr<IpaVerifyWork, void (*)(IpaVerifyWork*)> work(work_raw, ipa_verify_work_free);
     VK_TRY(d_chal.ensure(chunk * (size_t)(K + 1) * 32));
     VK_TRY(d_fr.ensure(chunk * 3 * 32));              // tip | y | point
     VK_TRY(d_pts.ensure(chunk * T * 64));             // C | L | R
-    VK_TRY(d_flags.ensure(chunk * (T + 1)));          // identity flags of C | L | R, then the bad bytes
-    VK_TRY(d_fixed.ensure(chunk * 65));               // the fixed rows' commitments and their flags
-    VK_TRY(d_pw.ensure(N * 32));
+    VK_TRY(d_flags.ensure(chunk * T));                // identity flags of C | L | R
     VK_TRY(d_res.ensure(n));
     hipStream_t st = ctx->stream;
     uint32_t* d_tip = d_fr.as<uint32_t>();
@@ -257,21 +335,6 @@ extern "C" int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n, co
     uint8_t* d_cinf = d_flags.as<uint8_t>();
     uint8_t* d_linf = d_cinf + chunk;
     uint8_t* d_rinf = d_linf + chunk * (size_t)K;
-    uint8_t* d_bad = d_rinf + chunk * (size_t)K;
-    uint8_t* d_fxy = d_fixed.as<uint8_t>();
-    uint8_t* d_finf = d_fxy + chunk * 64;
-    {  // the domain's powers, once per call
-        std::vector<Fr> pw(N);
-        const Fr omega = bn254_group_gen(N);
-        Fr w = fe_one<F>();
-        for (size_t i = 0; i < N; i++) {
-            pw[i] = w;
-            w = fe_mul<F>(w, omega);
-        }
-        VK_CHECK_HIP(hipMemcpyAsync(d_pw.p, pw.data(), N * 32, hipMemcpyHostToDevice, st));
-        VK_CHECK_HIP(hipStreamSynchronize(st));
-    }
-    const Fr n_inv = fe_inv_bin<F>(mont_from_u64<F>(N));
 
     // a chunk's challenges: [w, x_0 .. x_{K-1}] per proof (the transcripts advance as vc_ipa_verify's)
     double lap_tr = 0;
@@ -289,7 +352,7 @@ extern "C" int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n, co
         }
     } up;
     VK_CHECK_HIP(hipEventCreateWithFlags(&up.e, hipEventDisableTiming));
-    double lap_field = 0, lap_fixed = 0, lap_curve = 0;
+    double laps[3] = {0, 0, 0};  // field, fixed commit, curve
     const double call0 = timing ? clock_us() : 0.0;
     run_transcripts(0, chunk, chal[0]);
     size_t nchunks = 0;
@@ -321,31 +384,8 @@ extern "C" int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n, co
         VK_CHECK_HIP(hipMemcpyAsync(d_cinf, com_inf + lo, cnt, hipMemcpyHostToDevice, st));
         VK_CHECK_HIP(hipMemcpyAsync(d_linf, l_inf + lo * K, cnt * (size_t)K, hipMemcpyHostToDevice, st));
         VK_CHECK_HIP(hipMemcpyAsync(d_rinf, r_inf + lo * K, cnt * (size_t)K, hipMemcpyHostToDevice, st));
-        double c0 = 0;
-        if (timing) {
-            VK_CHECK_HIP(hipStreamSynchronize(st));
-            c0 = clock_us();
-        }
-        VK_LAUNCH(ctx, "ipa_verify_field", k_ipa_verify_field, cnt, 64, 0, d_chal.as<uint32_t>(), d_tip, d_y, d_point,
-                  d_pw.as<FrE>(), n_inv, (uint32_t)N, K, d_rows.as<uint32_t>(), d_vs.as<uint32_t>(), d_bad);
-        double c1 = 0;
-        if (timing) {
-            VK_CHECK_HIP(hipStreamSynchronize(st));
-            c1 = clock_us();
-        }
-        VK_TRY(msm_batch_run(ctx, t, N + 1, d_rows.p, cnt, /*mont=*/1, d_fxy, d_finf));
-        double c2 = 0;
-        if (timing) {
-            VK_CHECK_HIP(hipStreamSynchronize(st));
-            c2 = clock_us();
-        }
-        VK_LAUNCH(ctx, "ipa_verify_curve", k_ipa_verify_curve, (cnt * IPA_LP + 63) / 64, 64, 0, d_com, d_cinf, d_l,
-                  d_linf, d_r, d_rinf, d_vs.as<uint32_t>(), reinterpret_cast<const uint32_t*>(d_fxy), d_finf, d_bad, K,
-                  cnt, d_res.as<uint8_t>() + lo);
-        if (timing) {
-            VK_CHECK_HIP(hipStreamSynchronize(st));
-            lap_field += c1 - c0, lap_fixed += c2 - c1, lap_curve += clock_us() - c2;
-        }
+        VK_TRY(ipa_verify_dev(ctx, t, work.get(), cnt, d_chal.as<uint32_t>(), d_tip, d_y, d_point, d_com, d_cinf, d_l,
+                              d_linf, d_r, d_rinf, d_res.as<uint8_t>() + lo, timing ? laps : nullptr));
     }
     VK_CHECK_HIP(hipMemcpyAsync(results, d_res.p, n, hipMemcpyDeviceToHost, st));
     VK_CHECK_HIP(hipStreamSynchronize(st));
@@ -353,6 +393,6 @@ extern "C" int vc_ipa_verify_many(vc_ctx* ctx, int table, size_t N, size_t n, co
         fprintf(stderr,
                 "[ipa_verify_many] n=%zu N=%zu chunks=%zu: transcripts %.1f us (one chunk ahead of the device), "
                 "field %.1f us, fixed commit %.1f us, curve %.1f us, call %.1f us\n",
-                n, N, nchunks, lap_tr, lap_field, lap_fixed, lap_curve, clock_us() - call0);
+                n, N, nchunks, lap_tr, laps[0], laps[1], laps[2], clock_us() - call0);
     return VC_OK;
 }

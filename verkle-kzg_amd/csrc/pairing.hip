@@ -22,6 +22,7 @@
 
 #include "ctx.hpp"
 #include "pairing_internal.hpp"
+#include "scheme_internal.hpp"
 
 namespace vk {
 
@@ -115,6 +116,21 @@ int verify_many(vc_ctx* ctx, const KzgKey<C>& key, size_t n, const uint64_t* com
     return VC_OK;
 }
 }  // namespace
+
+// the kernel alone over device arrays (scheme_internal.hpp): the multiproof many-verifier's claims
+int kzg_verify_dev(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint32_t* d_com, const uint8_t* d_cinf,
+                   const uint32_t* d_points, const uint32_t* d_proof, const uint8_t* d_pinf, const uint32_t* d_y,
+                   uint8_t* d_out) {
+    using C = BN254Kzg;
+    if (!ctx || !vk || vk->curve != VC_CURVE_BN254 || ctx->curve != VC_CURVE_BN254) return VC_E_INVALID;
+    if (n == 0) return VC_OK;
+    const KzgKey<C>& key = kzg_key<C>(vk);
+    const LineCoefT<C::Fq>* d_lines = nullptr;
+    VK_TRY(cached_lines<C>(ctx, key, &d_lines));
+    VK_LAUNCH(ctx, C::VERIFY_LAUNCH, k_kzg_verify<C>, (n + 63) / 64, 64, 0, d_com, d_cinf, d_proof, d_pinf, d_y, d_points,
+              key.omega, (uint64_t)key.size, d_lines, n, d_out);
+    return VC_OK;
+}
 
 }  // namespace vk
 

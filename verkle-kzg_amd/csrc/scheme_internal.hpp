@@ -42,6 +42,21 @@ void ipa_host_challenges(size_t lo, size_t cnt, int K, const uint64_t* com_xy, c
 
 // ---- host helpers of the protocol layer, BN254 (scheme.hip describes them)
 struct Table;
+// ---- the inner many-verifiers over device arrays (the multiproof many-verifier, mp_verify.hip)
+// vc_ipa_verify_many's device half (ipa_verify.hip): a workspace for chunks of <= chunk proofs of
+// size N, then per chunk the field kernel, the fixed commit and the curve kernel over device
+// arrays in vc_ipa_verify_many's layouts (32-bit words) and device challenges [w, x_0 .. x_{K-1}]
+// (Montgomery). The point arrays are rewritten. laps: null, or {field, fixed commit, curve} sums in us.
+struct IpaVerifyWork;
+int ipa_verify_work_new(vc_ctx* ctx, size_t N, size_t chunk, IpaVerifyWork** out);
+void ipa_verify_work_free(IpaVerifyWork* w);
+int ipa_verify_dev(vc_ctx* ctx, Table* t, IpaVerifyWork* w, size_t cnt, const uint32_t* d_chal, const uint32_t* d_tip,
+                   const uint32_t* d_y, const uint32_t* d_point, uint32_t* d_com, const uint8_t* d_cinf, uint32_t* d_l,
+                   const uint8_t* d_linf, uint32_t* d_r, const uint8_t* d_rinf, uint8_t* d_out, double* laps);
+// vc_kzg_verify_many's kernel over device arrays, BN254 key (pairing.hip): n verdict bytes at d_out
+int kzg_verify_dev(vc_ctx* ctx, const vc_kzg_vk* vk, size_t n, const uint32_t* d_com, const uint8_t* d_cinf,
+                   const uint32_t* d_points, const uint32_t* d_proof, const uint8_t* d_pinf, const uint32_t* d_y,
+                   uint8_t* d_out);
 BN254G1::Acc acc_of(const uint64_t* xy, bool inf);  // canonical affine (or the identity) -> accumulator
 void aff_of(const BN254G1::Acc& a, uint64_t* xy, uint8_t* inf);
 std::vector<Fr> host_batch_inv(const std::vector<Fr>& v);  // 1 / 0 = 0

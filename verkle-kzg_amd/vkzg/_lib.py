@@ -154,6 +154,11 @@ SIGNATURES = {
     "vc_kzg_verify_batch": (c_int, [c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, P, ctypes.POINTER(c_int), P]),
     "vc_multiproof_verify_kzg": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, P, P, P, P, P, ctypes.c_uint8, P,
                                          ctypes.c_uint8, P, ctypes.POINTER(c_int)]),
+    "vc_multiproof_claims_many": (c_int, [c_void_p, c_size_t, c_size_t, P, c_size_t, P, P, P, P, P, P, P, P, P, P]),
+    "vc_multiproof_verify_many_ipa": (c_int, [c_void_p, c_int, c_size_t, c_size_t, P, c_size_t, P, P, P, P, P, P, P, P,
+                                              P, P, P, P, P]),
+    "vc_multiproof_verify_many_kzg": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, P, c_size_t, P, P, P, P, P, P, P,
+                                              P, P, P]),
     # vc_comm.h
     "vc_comm_unique_id": (c_int, [P]),
     "vc_comm_init_rccl": (c_int, [c_int, c_int, c_int, P, ctypes.POINTER(c_void_p)]),

@@ -1024,6 +1024,69 @@ def prove_multiproof_many(vc, cxy, cinf, z, y, d_data_ptr):
     return out.proofs()
 
 
+# ---------------------------------------------------------------- P multiproofs verified in one call
+MPV_Q_MAX = 4096  # VC_MPV_Q_MAX: queries per proof of the many-verifier
+
+
+def _queries_many(queries_per_proof):
+    """[[(commitment, z, y)]] -> (q_ptr, com_xy, com_inf, z, y) flat arrays. Values as given (low
+    256 bits): a malformed entry must reach the library unreduced."""
+    flat = [q for qs in queries_per_proof for q in qs]
+    q_ptr = np.zeros(len(queries_per_proof) + 1, dtype=np.uint64)
+    q_ptr[1:] = np.cumsum([len(qs) for qs in queries_per_proof], dtype=np.uint64)
+    cxy, cinf = _pt_arrays_many([q[0] for q in flat])
+    z = np.array([int(q[1]) for q in flat], dtype=np.uint64)
+    y = ints_to_limbs([int(q[2]) & _M256 for q in flat], 4) if flat else np.zeros((0, 4), dtype=np.uint64)
+    return q_ptr, cxy, cinf, z, y
+
+
+def multiproof_claims_many(vc, queries_per_proof, ds):
+    """(E - D, t) of P multiproofs in one call (vc_multiproof_claims_many): queries_per_proof P lists
+    of (commitment, z, y), ds the proofs' D points -> P entries {"commitment", "t"} as
+    verify_multiproof gives for KZG, or None for an entry with malformed content."""
+    P = len(queries_per_proof)
+    if P == 0:
+        return []
+    N = vc.N if isinstance(vc, IPA) else vc.size
+    q_ptr, cxy, cinf, z, y = _queries_many(queries_per_proof)
+    dxy, dinf = _pt_arrays_many(list(ds))
+    oxy = np.zeros((P, 8), dtype=np.uint64)
+    oinf = np.zeros(P, dtype=np.uint8)
+    t = np.zeros((P, 4), dtype=np.uint64)
+    bad = np.zeros(P, dtype=np.uint8)
+    check(lib().vc_multiproof_claims_many(vc.engine.h, N, P, _p(q_ptr), 0, _p(cxy), _p(cinf), _p(z), _p(y), _p(dxy),
+                                          _p(dinf), _p(oxy), _p(oinf), _p(t), _p(bad)), "multiproof_claims_many")
+    return [None if bad[p] else {"commitment": _pt(oxy[p], oinf[p]), "t": limbs_to_int(t[p])} for p in range(P)]
+
+
+def verify_multiproof_many(vc, queries_per_proof, mps):
+    """P multiproofs on the GPU, one verdict each (vc_multiproof_verify_many_ipa / _kzg) -> list of
+    bool. queries_per_proof: P lists of (commitment, z, y), ragged or not; mps: P {"proof", "d"} as
+    prove_multiproof / prove_multiproof_many return them. vc: the IPA or KZG scheme object (KZG: its
+    verifying key is used). VCError (VC_E_DOMAIN) when a z is not below N."""
+    P = len(mps)
+    if len(queries_per_proof) != P:
+        raise ValueError("one query list per proof")
+    if P == 0:
+        return []
+    q_ptr, cxy, cinf, z, y = _queries_many(queries_per_proof)
+    dxy, dinf = _pt_arrays_many([mp["d"] for mp in mps])
+    out = np.zeros(P, dtype=np.uint8)
+    if isinstance(vc, IPA):
+        proofs = [mp["proof"] for mp in mps]
+        (_, _, _, lxy, linf, rxy, rinf, tips, ys), good = vc._verify_many_arrays([None] * P, [0] * P, proofs)
+        check(lib().vc_multiproof_verify_many_ipa(vc.engine.h, vc.table, vc.N, P, _p(q_ptr), 0, _p(cxy), _p(cinf), _p(z),
+                                                  _p(y), _p(dxy), _p(dinf), _p(lxy), _p(linf), _p(rxy), _p(rinf),
+                                                  _p(tips), _p(ys), _p(out)), "multiproof_verify_many_ipa")
+        return [bool(v) and g for v, g in zip(out, good)]
+    kxy, kinf = _pt_arrays_many([mp["proof"]["proof"] for mp in mps])
+    ky = ints_to_limbs([int(mp["proof"]["y"]) & _M256 for mp in mps], 4)
+    check(lib().vc_multiproof_verify_many_kzg(vc.engine.h, vc.verifying_key().h, vc.size, P, _p(q_ptr), 0, _p(cxy),
+                                              _p(cinf), _p(z), _p(y), _p(dxy), _p(dinf), _p(kxy), _p(kinf), _p(ky),
+                                              _p(out)), "multiproof_verify_many_kzg")
+    return [bool(v) for v in out]
+
+
 # ---------------------------------------------------------------- sharded multiproof (SURVEY 8(e) C5)
 def multiproof_begin(N, cxy, cinf, z, y):
     """Phase 1 (host, every rank): transcript over all queries -> (transcript handle, r limbs, rows)."""
